@@ -25,6 +25,13 @@ Prints ONE JSON line on rank 0 with
   cpu_baseline            the oracle on the host cores (N = 1 only, bounded sample: median of 5 forwards)
   other_workloads         BASELINE configs[2] (PTv3 semseg on a 120k-point LiDAR-like scan, with its own roofline),
                           configs[4] (Swin3D-S), configs[3]'s per-GPU share (one training step, with its roofline)
+
+--dump-outputs DIR writes, on rank 0, what the last timed step of the measured path returned, as DIR/<name>.npy
+(float32; float64 stays float64): forward mode the model's result dict (`pred`, or `seg_logits` with --model semseg);
+train mode the result dict of the training forward (loss and its parts) and the parameters and gradients after the step,
+each flattened in named_parameters() order.  Past 64 MB in all, every array keeps the same seeded sample of its rows.
+Scenes, weights and every RNG draw are fixed by the arguments, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -146,7 +153,12 @@ def parse(argv=None):
     ap.add_argument("--rehearse-launch", action="store_true",
                     help="no GPU work: exercise launch, rendezvous (gloo), sharding and reductions only; the JSON "
                          "line then carries value null and rehearsal true (never a reported number)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0, at most 64 MB in all)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # --------------------------------------------------------------------------------------------------
@@ -292,6 +304,38 @@ def cpu_baseline(sd, cfg, model, device, n_points):
 
 
 # --------------------------------------------------------------------------------------------------
+# --dump-outputs
+# --------------------------------------------------------------------------------------------------
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def host_arrays(result):
+    """The tensors of a result dict as host arrays: float64 stays float64, integers become float64 (exact), the rest
+    float32."""
+    out = {}
+    for k, v in result.items():
+        if torch.is_tensor(v):
+            v = v.detach()
+            out[k] = (v.double() if v.dtype == torch.float64 or not v.is_floating_point() else v.float()).cpu().numpy()
+    return out
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BYTES):
+    """np.save every array as out_dir/<name>.npy ('/' in a name becomes '_').  Past `budget` bytes in all, every array
+    keeps the same fraction of its rows, drawn with a fixed seed: the same rows in every run, and the same rows of
+    arrays of the same length (parameters and their gradients)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 1.0 if total <= budget else (budget - (1 << 16)) / total   # 64 kB left for the .npy headers and scalars
+    for name, a in arrays.items():
+        if frac < 1.0 and a.ndim and len(a) > 1:
+            rows = np.random.default_rng(0).choice(len(a), max(1, int(len(a) * frac)), replace=False, shuffle=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(out_dir, name.replace("/", "_") + ".npy"), a)
+
+
+# --------------------------------------------------------------------------------------------------
 # timing helpers
 # --------------------------------------------------------------------------------------------------
 def timed_steps(step, steps, warmup, world, device):
@@ -335,18 +379,23 @@ def synced_steps(step, steps, warmup, world, device):
 
 
 def forward_figures(model, batch, key, args, world, device, overlap):
-    """elapsed of K synchronised single forwards, their median (ms), elapsed of K forwards in throughput mode, step fn"""
+    """elapsed of K synchronised single forwards, their median (ms), elapsed of K forwards in throughput mode, step fn,
+    host copy of the result dict of the last timed forward"""
+    last = {}
+
     def step():
         with torch.no_grad():
-            return model(batch)[key]
+            last["out"] = model(batch)
+        return last["out"][key]
     model.backbone.overlap_calls = False
     elapsed, lat = synced_steps(step, args.steps, args.warmup, world, device)
     model.backbone.overlap_calls = overlap
     thr = timed_steps(step, args.steps, args.warmup, world, device)
+    outputs = host_arrays(last["out"])
     model.backbone.overlap_calls = False
     step()
     torch.cuda.synchronize()
-    return elapsed, lat, thr, step
+    return elapsed, lat, thr, step, outputs
 
 
 def kernel_roofline(step, steps, dtype_name, rank=0):
@@ -408,7 +457,7 @@ def semseg_lidar_workload(device, args, world):
     model.backbone.compute_dtype = torch.bfloat16
     model.backbone.inputs_resident = True
     batch = {k: v.to(device) for k, v in S.collate([make_scene(120000, "lidar", 1000)]).items()}
-    elapsed, lat, thr, step = forward_figures(model, batch, "seg_logits", args, world, device, True)
+    elapsed, lat, thr, step, _ = forward_figures(model, batch, "seg_logits", args, world, device, True)
     roof = kernel_roofline(step, args.steps, "bf16")
     with torch.no_grad():
         pts = model(batch, return_point=True)["point"]["_stage_points"]
@@ -445,8 +494,8 @@ def train_step_workload(device, args):
         opt.step()
         last["loss"] = out["loss"]
 
-    steps = 10
-    elapsed = timed_steps(step, steps, 3, 1, device)
+    steps = args.steps
+    elapsed = timed_steps(step, steps, args.warmup, 1, device)
     roof = kernel_roofline(step, steps, "bf16")
     return {"workload": "OffsetKeypointPTv3 (fork config, 46.2M params) train step: forward + backward + fused AdamW, "
                         "1 x 100000-point scene, bf16 activations, drop_path 0.3", "value": round(1e5 * steps / elapsed / 1e6, 4),
@@ -454,7 +503,7 @@ def train_step_workload(device, args):
             "roofline": roof}
 
 
-def swin3d_workload(device, points=1000000):
+def swin3d_workload(device, args, points=1000000):
     """BASELINE configs[4] beside the headline: "Swin3D-v1m1" (Swin3D-S, the S3DIS config: 9 input channels, colour + normal
     signals, 5^3 / 7^3-voxel windows with cRSE tables) forward on one ~1M-point room-like scene (an S3DIS Area-5 room at
     the 2 cm base grid).  fp32, random weights; PARITY UNPINNED (MinkowskiEngine / microsoft/Swin3D are not in the
@@ -481,14 +530,14 @@ def swin3d_workload(device, points=1000000):
     def step():
         with torch.no_grad():
             out["y"] = model(dict(batch))
-    reps = 5
+    reps, warmup = args.steps, args.warmup
     ts = []
-    for i in range(2 + reps):
+    for i in range(warmup + reps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         step()
         torch.cuda.synchronize()
-        if i >= 2:
+        if i >= warmup:
             ts.append((time.perf_counter() - t0) * 1e3)
     ms = statistics.median(ts)
     roof = kernel_roofline(step, 3, "fp32")
@@ -496,12 +545,12 @@ def swin3d_workload(device, points=1000000):
     # the reference's S3DIS configs set enable_amp = True: the same forward with bf16 features / GEMM operands / q, k, v
     model.compute_dtype = torch.bfloat16
     tb = []
-    for i in range(2 + reps):
+    for i in range(warmup + reps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         step()
         torch.cuda.synchronize()
-        if i >= 2:
+        if i >= warmup:
             tb.append((time.perf_counter() - t0) * 1e3)
     mb = statistics.median(tb)
     return {"workload": f"Swin3D-v1m1 (Swin3D-S, S3DIS config, 28.2M params) eval forward, 1 x {n}-point room-like scene, "
@@ -540,12 +589,22 @@ def train_bench(args, model, device, world, rank, local_rank):
         out = net(batch)
         out["loss"].backward()
         opt.step()
-        last["loss"] = out["loss"]
+        last["out"] = out
 
     elapsed = timed_steps(step, args.steps, args.warmup, world, device)
+    outputs = None
+    if args.dump_outputs and rank == 0:   # before the roofline steps move the parameters on
+        params = list(model.parameters())
+        outputs = host_arrays(last["out"])
+        outputs.update(host_arrays({
+            "params": torch.cat([p.detach().reshape(-1).float() for p in params]),
+            "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                for p in params])}))
     total_points = reduce_over_ranks(n_points, device, dist.ReduceOp.SUM)
     probe = allreduce_probe(device, GRAD_BYTES) if world > 1 else None
     roof = kernel_roofline(step, args.steps, args.dtype, rank) if not args.no_kernel_events else None
+    if outputs is not None:
+        dump_outputs(outputs, args.dump_outputs)
     if rank == 0:
         print(json.dumps({
             "metric": "Mpoints/sec PTv3 train step (fwd+bwd+AdamW) @100k pts/scene, 1024-pt window",
@@ -560,7 +619,7 @@ def train_bench(args, model, device, world, rank, local_rank):
                        "parallelism": f"dp{world} (DDP over RCCL, {GRAD_BYTES / 1e6:.1f} MB fp32 gradient all-reduce)"
                        if world > 1 else "dp1"},
             "rccl_ranks": world, "allreduce_probe": probe,
-            "roofline": roof, "cpu_baseline": None, "final_loss": float(last["loss"].item())}), flush=True)
+            "roofline": roof, "cpu_baseline": None, "final_loss": float(last["out"]["loss"].item())}), flush=True)
     if world > 1:
         dist.destroy_process_group()
 
@@ -632,7 +691,8 @@ def run(args):
     # two forwards in flight (the small deep levels of step i run under the chip-filling level-0 kernels of step
     # i+1); every step is still one complete forward of the scene and all of them finish inside the timed region.
     # Then SURVEY 8(d)'s figure: the median of single, synchronize-bracketed forwards (one in flight).
-    elapsed, latency, thr, step = forward_figures(model, batch, out_key, args, world, device, not args.no_overlap)
+    elapsed, latency, thr, step, outputs = forward_figures(model, batch, out_key, args, world, device,
+                                                           not args.no_overlap)
     total_points = reduce_over_ranks(n_points, device, dist.ReduceOp.SUM)
 
     # ---- kernel durations: the SAME K steps again with HIP events on the launch stream around every matrix-core launch
@@ -646,7 +706,7 @@ def run(args):
     default_run = world == 1 and not args.no_extra and args.model == "offset"
     if default_run and args.dtype == "bf16":
         model.backbone.compute_dtype = torch.float32
-        e32, l32, t32, _ = forward_figures(model, batch, out_key, args, world, device, not args.no_overlap)
+        e32, l32, t32, _, _ = forward_figures(model, batch, out_key, args, world, device, not args.no_overlap)
         fp32 = {"value": round(n_points * args.steps / e32 / 1e6, 4), "unit": "Mpoints/s",
                 "ms_per_step": round(e32 / args.steps * 1e3, 3), "latency_ms_median": round(l32, 3),
                 "throughput_2_in_flight": {"value": round(n_points * args.steps / t32 / 1e6, 4),
@@ -657,7 +717,7 @@ def run(args):
         torch.cuda.empty_cache()
         extra = {"semseg_lidar_120k": semseg_lidar_workload(device, args, world)}
         torch.cuda.empty_cache()
-        extra["swin3d_s3dis_1m"] = swin3d_workload(device)
+        extra["swin3d_s3dis_1m"] = swin3d_workload(device, args)
         torch.cuda.empty_cache()
         extra["train_step_100k"] = train_step_workload(device, args)
 
@@ -688,6 +748,8 @@ def run(args):
             "pmc_replayed": pmc_replayed("lidar" if args.kind == "lidar" else "default", roofline["kernel"] if roofline else None)
             if (args.points, args.scenes, args.dtype) in ((100000, 1, "bf16"), (120000, 1, "bf16")) else None,
         }
+        if args.dump_outputs:
+            dump_outputs(outputs, args.dump_outputs)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

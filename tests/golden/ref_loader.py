@@ -1,7 +1,7 @@
 """Build-container-only helper: import the reference's hot-path Python files in place.
 
-Used ONLY by tests/golden/make_golden.py (which writes the committed *.npz fixtures) and by
-tests that are skipped when /root/reference is absent.  Nothing from /root/reference is
+Used ONLY by the tests/golden/make_golden*.py scripts (which write the committed fixtures); no
+test imports it, so the suite runs without the reference tree.  Nothing from /root/reference is
 copied; the files are imported where they lie.  The reference's package __init__ files pull
 in CUDA-only wheels (spconv, MinkowskiEngine, ocnn, pointops, torch_scatter ...), so bare
 package objects are pre-registered and four tiny third-party stubs are installed:
