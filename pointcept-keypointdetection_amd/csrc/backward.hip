@@ -809,7 +809,8 @@ extern "C" int ptv3_col_reduce(const void* a, const void* b, const float* mu, co
   BWD_DTYPE_CHECK("col_reduce");
   PTV3_REQUIRE(mode >= 0 && mode <= 3, "col_reduce: mode %d outside [0,3]", mode);
   PTV3_REQUIRE(mode != 3 || mu, "col_reduce: mode 3 needs mu");
-  PTV3_REQUIRE(mode != 2 || (b && mu && rs), "col_reduce: mode 2 needs b, mu, rs");
+  // an empty b (m = 0) has no storage: only mu and rs are required then
+  PTV3_REQUIRE(mode != 2 || ((b || m == 0) && mu && rs), "col_reduce: mode 2 needs b, mu, rs");
   PTV3_REQUIRE(c > 0 && m >= 0, "col_reduce: bad shape");
   hipStream_t s = (hipStream_t)stream;
   const int nq = mode == 0 ? 1 : 2;

@@ -209,7 +209,8 @@ __device__ __forceinline__ void unit_gemm(const char* buf, int slice_rows, const
 
 // Output rows leave through BUFFER stores: a row at or past m lands beyond the descriptor's num_records and is dropped
 // by the hardware, so every store instruction is issued by every wave, branch-free - the counted waits of the unit
-// loop rely on that count.  (m x ld x sizeof(T) + one tile must stay below 4 GB: checked by the launcher.)
+// loop rely on that count.  (num_records is an int: m x ld x sizeof(T) must stay below 2^31 - 2^20 bytes, checked by
+// ptv3_block_fusable / rows_linear_capable.)
 template <typename T>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t out_rsrc(T* base, int64_t m, int64_t ld) {
   return __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)(m * ld * (int64_t)sizeof(T)), 0x00020000);

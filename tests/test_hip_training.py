@@ -37,16 +37,22 @@ def _rel(got, ref, floor=1e-6):
     return (got.detach().float().cpu() - ref).abs().max().item() / max(ref.abs().max().item(), floor)
 
 
-@pytest.mark.parametrize("cfg_name,sizes,hidden", [("tiny", [900, 700], 32), ("fork", [5000, 3000], 256)])
-def test_train_step_vs_oracle_autograd(dev, cfg_name, sizes, hidden):
+@pytest.mark.parametrize("cfg_name,sizes,hidden,extent,cin", [
+    pytest.param("tiny", [900, 700], 32, 96, 4, id="tiny-sizes0-32"),
+    pytest.param("fork", [5000, 3000], 256, 96, 4, id="fork-sizes1-256"),
+    # bench.py --mode train's scene size: other weight-gradient (tn_chunks) and reduction (col_chunks) splits
+    pytest.param("fork", [100000], 256, None, 4, id="fork-bench100k-256"),
+    # xyz + rgb: the stem's K is padded to the granule and its weight gradient sliced back to 6 input channels
+    pytest.param("tiny", [900, 700], 32, 96, 6, id="tiny-cin6-32")])
+def test_train_step_vs_oracle_autograd(dev, cfg_name, sizes, hidden, extent, cin):
     from oracle import ptv3 as O
     import ptv3_scenes as S
-    cfg = dict(TINY_CFG if cfg_name == "tiny" else FORK_CFG, drop_path=0.0)
+    cfg = dict(TINY_CFG if cfg_name == "tiny" else FORK_CFG, drop_path=0.0, in_channels=cin)
     torch.manual_seed(1234)
     model = _build(cfg, hidden_dim=hidden)
     _perturb_stats(model)
     sd = {k: v.clone() for k, v in model.state_dict().items()}
-    data = S.make_batch(sizes, in_channels=4, extent=96, seed=21, with_target=6)
+    data = S.make_batch(sizes, in_channels=cin, extent=extent, seed=21, with_target=6)
     # ---- reference: torch autograd over the oracle
     orc = O.OffsetKeypointOracle(cfg, sd, training=True)
     torch.manual_seed(5)
@@ -70,6 +76,9 @@ def test_train_step_vs_oracle_autograd(dev, cfg_name, sizes, hidden):
     worst = max(((n, _rel(p.grad, ref_grads[n], 1e-3 * gmax)) for n, p in model.named_parameters()),
                 key=lambda t: t[1])
     assert worst[1] < 2e-3, worst
+    stem = "backbone.embedding.stem.conv.weight"
+    sw = dict(model.named_parameters())[stem]
+    assert sw.grad.shape == sw.shape == (cfg["enc_channels"][0], 5, 5, 5, cin)
     for n, b in model.named_buffers():
         if n.endswith(("running_mean", "running_var")):
             assert _rel(b, ref_bufs[n]) < 1e-4, n
@@ -85,6 +94,67 @@ def test_train_step_vs_oracle_autograd(dev, cfg_name, sizes, hidden):
     torch.optim.AdamW(groups(twin), lr=2e-3, weight_decay=0.05).step()
     for (n, p), q in zip(model.named_parameters(), twin.parameters()):
         assert (p - q).abs().max().item() < 1e-6, n
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_train_step_with_six_input_channels(dev, dtype):
+    """Fork config, xyz + rgb input (in_channels = 6, BASELINE configs 0 and 3): the stem pads K to the granule (8 in
+    both dtypes here) and slices its weight gradient back.  The step must equal, bit for bit, the step of the same
+    model given two zero input channels (in_channels = 8: no padding anywhere); in fp32 the loss, the stem weight
+    gradient (32, 5, 5, 5, 6) and the running statistics are checked against oracle autograd as in
+    test_train_step_vs_oracle_autograd.  (The remaining gradients are compared to the oracle in the cases above: on
+    this scene one output channel of enc4's pooling projection takes the other side of a near-tie in the segment max
+    in fp32 on the two sides, a 1e-2 difference confined to that channel, the same in the zero-padded model.)"""
+    from oracle import ptv3 as O
+    import ptv3_scenes as S
+    stem = "backbone.embedding.stem.conv.weight"
+
+    def step(cfg, sd, data):
+        torch.manual_seed(1234)
+        model = _build(cfg)
+        model.load_state_dict(sd)
+        model = model.to(dev).train()
+        model.backbone.compute_dtype = dtype
+        torch.manual_seed(5)
+        out = model({k: v.to(dev) for k, v in data.items()})
+        out["loss"].backward()
+        return out["loss"].detach(), model
+
+    cfg = dict(FORK_CFG, drop_path=0.0, in_channels=6)
+    torch.manual_seed(1234)
+    model = _build(cfg)
+    _perturb_stats(model)
+    sd = {k: v.clone() for k, v in model.state_dict().items()}
+    data = S.make_batch([5000, 3000], in_channels=6, extent=96, seed=21, with_target=6)
+    loss6, m6 = step(cfg, sd, data)
+    sd8 = dict(sd, **{stem: torch.nn.functional.pad(sd[stem], (0, 2))})
+    data8 = dict(data, feat=torch.nn.functional.pad(data["feat"], (0, 2)))
+    loss8, m8 = step(dict(cfg, in_channels=8), sd8, data8)
+    p6, p8 = dict(m6.named_parameters()), dict(m8.named_parameters())
+    assert p6[stem].grad.shape == p6[stem].shape == (32, 5, 5, 5, 6)
+    assert torch.equal(loss6, loss8)
+    assert torch.equal(p6[stem].grad, p8[stem].grad[..., :6])
+    assert not p8[stem].grad[..., 6:].any()                 # zero input channels get a zero weight gradient
+    for n, p in p6.items():
+        if n != stem:
+            assert torch.equal(p.grad, p8[n].grad), n
+    b8 = dict(m8.named_buffers())
+    for n, b in m6.named_buffers():
+        assert torch.equal(b, b8[n]), n
+    if dtype == torch.bfloat16:
+        return
+    orc = O.OffsetKeypointOracle(cfg, sd, training=True)
+    torch.manual_seed(5)
+    ref = orc.forward(data)
+    ref["loss"].backward()
+    ref_grads = {k: v.grad for k, v in orc.named_parameters()}
+    assert abs(loss6.item() - ref["loss"].item()) < 1e-4
+    gmax = max(g.abs().max().item() for g in ref_grads.values())
+    assert _rel(p6[stem].grad, ref_grads[stem], 1e-3 * gmax) < 2e-3
+    ref_bufs = dict(orc.named_buffers())
+    for n, b in m6.named_buffers():
+        if n.endswith(("running_mean", "running_var")):
+            assert _rel(b, ref_bufs[n]) < 1e-4, n
 
 
 def test_train_step_bf16_close_to_fp32(dev):
