@@ -12,10 +12,12 @@ rank.  Without them, `--gpus N` with N > 1 starts N child processes ITSELF befor
 process per GPU, `init_process_group("nccl")` over tcp://127.0.0.1:<free port>, the process model of the
 reference's pointcept/engines/launch.py:36-113 - and returns their exit code.
 
-Prints ONE JSON line on rank 0 with
+Prints ONE JSON line on rank 0.  A plain run measures the headline alone: it sets up, warms up, times the K steps,
+writes its outputs if asked and prints
   value / ms_per_step     SURVEY 8(d)'s figure: K single forwards, each followed by torch.cuda.synchronize(), timed as
                           one region between barrier + synchronize (one forward in flight at any time)
   latency_ms_median       the median of those K single forwards (and latency_mpoints_per_s)
+With --full the run goes on to measure and check everything else (each of these is null in a plain run):
   throughput_2_in_flight  the same K forwards WITHOUT the per-step synchronize, two in flight (the executor's
                           throughput mode); --no-overlap: one in flight, back to back
   fp32                    the same figures in fp32 (exact-fp32 MFMA), the arithmetic of the 1e-4 parity bar
@@ -25,9 +27,13 @@ Prints ONE JSON line on rank 0 with
   cpu_baseline            the oracle on the host cores (N = 1 only, bounded sample: median of 5 forwards)
   other_workloads         BASELINE configs[2] (PTv3 semseg on a 120k-point LiDAR-like scan, with its own roofline),
                           configs[4] (Swin3D-S), configs[3]'s per-GPU share (one training step, with its roofline)
+  allreduce_probe         --mode train, N > 1: a timed all-reduce of a buffer the size of the gradient
+--cpu-sample, --no-kernel-events and --no-extra trim what --full adds.  Both runs time the same K steps: a plain run
+first makes the order-shuffle draws (torch's CPU generator) of the parity forward that --full makes at that point.
 
---dump-outputs DIR writes, on rank 0, what the last timed step of the measured path returned, as DIR/<name>.npy
-(float32; float64 stays float64): forward mode the model's result dict (`pred`, or `seg_logits` with --model semseg);
+--dump-outputs DIR writes, on rank 0, what the last timed step returned, as DIR/<name>.npy (float32; float64 stays
+float64): forward mode the model's result dict (`pred`, or `seg_logits` with --model semseg) of the last forward of the
+throughput-mode steps (a plain run makes those W + K forwards, untimed, only when it dumps);
 train mode the result dict of the training forward (loss and its parts) and the parameters and gradients after the step,
 each flattened in named_parameters() order.  Past 64 MB in all, every array keeps the same seeded sample of its rows.
 Scenes, weights and every RNG draw are fixed by the arguments, so two builds run with the same arguments can be
@@ -142,9 +148,13 @@ def parse(argv=None):
     ap.add_argument("--model", default="offset", choices=["offset", "semseg"],
                     help="offset = OffsetKeypointPTv3 over the fork config (headline); semseg = DefaultSegmentorV2 "
                          "(19 classes) over the upstream PTv3 semseg backbone (enable_flash=True), BASELINE configs[2]")
-    ap.add_argument("--cpu-sample", type=int, default=100000, help="points of the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--no-kernel-events", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the fp32 line and the configs[2] workload")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline too: throughput mode, fp32, CPU baseline "
+                         "and parity, roofline, the other workloads, the all-reduce probe (a plain run: headline only)")
+    ap.add_argument("--cpu-sample", type=int, default=100000,
+                    help="--full: points of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full: skip the roofline steps")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the fp32 line and the other workloads")
     ap.add_argument("--no-overlap", action="store_true",
                     help="forward mode: do not let consecutive forwards overlap (one feature pipeline in flight)")
     ap.add_argument("--mode", default="forward", choices=["forward", "train"],
@@ -378,9 +388,10 @@ def synced_steps(step, steps, warmup, world, device):
     return reduce_over_ranks(time.perf_counter() - t0, device, dist.ReduceOp.MAX), statistics.median(ts)
 
 
-def forward_figures(model, batch, key, args, world, device, overlap):
+def forward_figures(model, batch, key, args, world, device, overlap, throughput=True):
     """elapsed of K synchronised single forwards, their median (ms), elapsed of K forwards in throughput mode, step fn,
-    host copy of the result dict of the last timed forward"""
+    host copy of the result dict of the last timed forward.  throughput=False stops after the synchronised forwards
+    (elapsed of the throughput mode None, result dict of the last synchronised forward)."""
     last = {}
 
     def step():
@@ -389,6 +400,8 @@ def forward_figures(model, batch, key, args, world, device, overlap):
         return last["out"][key]
     model.backbone.overlap_calls = False
     elapsed, lat = synced_steps(step, args.steps, args.warmup, world, device)
+    if not throughput:
+        return elapsed, lat, None, step, host_arrays(last["out"])
     model.backbone.overlap_calls = overlap
     thr = timed_steps(step, args.steps, args.warmup, world, device)
     outputs = host_arrays(last["out"])
@@ -601,8 +614,8 @@ def train_bench(args, model, device, world, rank, local_rank):
             "grads": torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
                                 for p in params])}))
     total_points = reduce_over_ranks(n_points, device, dist.ReduceOp.SUM)
-    probe = allreduce_probe(device, GRAD_BYTES) if world > 1 else None
-    roof = kernel_roofline(step, args.steps, args.dtype, rank) if not args.no_kernel_events else None
+    probe = allreduce_probe(device, GRAD_BYTES) if args.full and world > 1 else None
+    roof = kernel_roofline(step, args.steps, args.dtype, rank) if args.full and not args.no_kernel_events else None
     if outputs is not None:
         dump_outputs(outputs, args.dump_outputs)
     if rank == 0:
@@ -619,7 +632,8 @@ def train_bench(args, model, device, world, rank, local_rank):
                        "parallelism": f"dp{world} (DDP over RCCL, {GRAD_BYTES / 1e6:.1f} MB fp32 gradient all-reduce)"
                        if world > 1 else "dp1"},
             "rccl_ranks": world, "allreduce_probe": probe,
-            "roofline": roof, "cpu_baseline": None, "final_loss": float(last["out"]["loss"].item())}), flush=True)
+            "roofline": roof, "cpu_baseline": None, "final_loss": float(last["out"]["loss"].item()),
+            "full": args.full}), flush=True)
     if world > 1:
         dist.destroy_process_group()
 
@@ -676,7 +690,8 @@ def run(args):
     cpu, parity = None, None
     if args.mode == "train":
         return train_bench(args, model, device, world, rank, dev_index)
-    if rank == 0 and world == 1 and args.cpu_sample > 0 and args.model == "offset":
+    parity_leg = rank == 0 and world == 1 and args.cpu_sample > 0 and args.model == "offset"
+    if parity_leg and args.full:
         cpu, parity = cpu_baseline(sd, cfg, model, device, args.cpu_sample)
 
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
@@ -686,24 +701,32 @@ def run(args):
     scenes = [make_scene(args.points, args.kind, seed) for seed in rank_scene_seeds(rank, args.scenes)]
     batch = {k: v.to(device) for k, v in S.collate(scenes).items()}
     n_points = args.points * args.scenes
+    if parity_leg and not args.full:
+        # every forward draws its serialization-order shuffles from torch's CPU generator: leave it where the parity
+        # leg of --full leaves it (seed 11, then one forward), so that both runs time the same K forwards
+        torch.manual_seed(11)
+        with torch.no_grad():
+            model(batch)
+        torch.cuda.synchronize()
 
     # ---- timed region: K steps, nothing but the forward (barrier + synchronize on both sides).  Throughput mode:
     # two forwards in flight (the small deep levels of step i run under the chip-filling level-0 kernels of step
     # i+1); every step is still one complete forward of the scene and all of them finish inside the timed region.
     # Then SURVEY 8(d)'s figure: the median of single, synchronize-bracketed forwards (one in flight).
+    # A plain run stops after the synchronised forwards, unless it dumps: what it dumps comes from the throughput mode.
     elapsed, latency, thr, step, outputs = forward_figures(model, batch, out_key, args, world, device,
-                                                           not args.no_overlap)
+                                                           not args.no_overlap, args.full or bool(args.dump_outputs))
     total_points = reduce_over_ranks(n_points, device, dist.ReduceOp.SUM)
 
     # ---- kernel durations: the SAME K steps again with HIP events on the launch stream around every matrix-core launch
     roofline = None
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         model.backbone.overlap_calls = False
         roofline = kernel_roofline(step, args.steps, args.dtype, rank)
 
     # ---- the same workload in fp32 (the arithmetic of the 1e-4 parity bar), and BASELINE configs[2]
     fp32, extra = None, None
-    default_run = world == 1 and not args.no_extra and args.model == "offset"
+    default_run = args.full and world == 1 and not args.no_extra and args.model == "offset"
     if default_run and args.dtype == "bf16":
         model.backbone.compute_dtype = torch.float32
         e32, l32, t32, _, _ = forward_figures(model, batch, out_key, args, world, device, not args.no_overlap)
@@ -723,6 +746,7 @@ def run(args):
 
     if rank == 0:
         ms = elapsed / args.steps * 1e3
+        replay = args.full and (args.points, args.scenes, args.dtype) in ((100000, 1, "bf16"), (120000, 1, "bf16"))
         name = ("OffsetKeypointPTv3 (PT-v3m1 fork config, 46.2M params)" if args.model == "offset" else
                 "DefaultSegmentorV2 (19 classes, PT-v3m1 fork widths, enable_flash=True)")
         line = {
@@ -741,12 +765,13 @@ def run(args):
             "latency_mpoints_per_s": round(n_points / latency / 1e3, 4),
             "throughput_2_in_flight": {"value": round(total_points * args.steps / thr / 1e6, 4), "unit": "Mpoints/s",
                                        "ms_per_step": round(thr / args.steps * 1e3, 3),
-                                       "forwards_in_flight": 1 if args.no_overlap else 2},
+                                       "forwards_in_flight": 1 if args.no_overlap else 2} if args.full else None,
             "rccl_ranks": seen,
             "fp32": fp32,
             "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "other_workloads": extra,
             "pmc_replayed": pmc_replayed("lidar" if args.kind == "lidar" else "default", roofline["kernel"] if roofline else None)
-            if (args.points, args.scenes, args.dtype) in ((100000, 1, "bf16"), (120000, 1, "bf16")) else None,
+            if replay else None,
+            "full": args.full,
         }
         if args.dump_outputs:
             dump_outputs(outputs, args.dump_outputs)

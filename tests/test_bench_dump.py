@@ -29,6 +29,11 @@ def test_host_arrays_dtypes():
     assert got["loss"].shape == () and got["loss"] == 0.5
 
 
+def test_full_is_off_by_default():
+    bench = _bench()
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+
+
 def test_dump_outputs_budget_and_fixed_sample(tmp_path):
     bench = _bench()
     rng = np.random.default_rng(5)
@@ -50,8 +55,8 @@ def test_dump_outputs_budget_and_fixed_sample(tmp_path):
         assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
 
 
-def _run_bench(args, out_dir):
-    env = dict(os.environ)
+def _run_bench(args, out_dir, **env_vars):
+    env = dict(os.environ, **env_vars)
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", str(out_dir)]
                        + args, env=env, capture_output=True, text=True, timeout=900)
@@ -81,3 +86,23 @@ def test_bench_dump_outputs(tmp_path):
     assert float(t["loss"]) == pytest.approx(line["final_loss"], rel=1e-6)
     assert 0 < len(t["params"]) == len(t["grads"]) < 46181592      # sampled: the whole model is past 64 MB
     assert np.isfinite(t["params"]).all() and np.isfinite(t["grads"]).all() and np.abs(t["grads"]).max() > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_times_and_dumps_what_full_run_does(tmp_path):
+    """A plain run reports the headline alone; --full adds the rest.  Both time the same forwards: the plain run makes
+    the order-shuffle draws of the parity leg it skips, so the two dump the same `pred`."""
+    args = ["--steps", "3", "--warmup", "1", "--points", "20000", "--cpu-sample", "100000", "--no-extra",
+            "--no-kernel-events"]
+    plain, a = _run_bench(args, tmp_path / "plain", PTV3_BENCH_CPU_REPS="1")
+    full, b = _run_bench(args + ["--full"], tmp_path / "full", PTV3_BENCH_CPU_REPS="1")
+    assert plain["full"] is False and full["full"] is True
+    for line in (plain, full):
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert line["latency_ms_median"] > 0
+    for key in ("throughput_2_in_flight", "cpu_baseline", "parity", "fp32", "roofline", "other_workloads"):
+        assert plain[key] is None, key
+    assert full["throughput_2_in_flight"]["value"] > 0 and full["cpu_baseline"]["value"] > 0
+    assert full["parity"]["fp32"]["offset_l2_max"] < 1e-4
+    assert sorted(a) == sorted(b) == ["pred"]
+    assert np.abs(a["pred"] - b["pred"]).max() <= 1e-3

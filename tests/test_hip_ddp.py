@@ -201,8 +201,8 @@ def test_bench_train_two_ranks_self_launch(tmp_path):
     env = dict(os.environ, PTV3_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "train", "--gpus", "2", "--steps", "2",
-                        "--warmup", "1", "--points", "20000", "--no-kernel-events"], env=env, capture_output=True,
-                       text=True, timeout=600)
+                        "--warmup", "1", "--points", "20000", "--no-kernel-events", "--full"],  # the all-reduce probe
+                       env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')][-1])
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2 and line["value"] > 0

@@ -10,23 +10,23 @@ export TMPDIR=/tmp
 # NOTE: only gpurun_out/ travels back from the GPU box; copy the summaries into profiles/$R afterwards with
 #       tools/collect_round.sh $R (runs in the build container).
 if [[ $PART == *A* ]]; then
-python bench.py > $O/bench_default.log 2>&1; grep '^{"metric"' $O/bench_default.log | tail -1 > $O/bench_n1_default.json
+python bench.py --full > $O/bench_default.log 2>&1; grep '^{"metric"' $O/bench_default.log | tail -1 > $O/bench_n1_default.json
 echo "bench done: $(cut -c1-160 $O/bench_n1_default.json)"
 fi
 pmc_pair() {  # $1 = tag, rest = bench args: FETCH / WRITE passes + SQ pass of one workload
   local tag=$1; shift
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf $O/pmc_${tag}_$c
-    rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_${tag}_$c -- python bench.py "$@" --steps 5 --warmup 2 --cpu-sample 0 --no-extra --no-kernel-events > $O/pmc_${tag}_$c.log 2>&1
+    rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/pmc_${tag}_$c -- python bench.py "$@" --full --steps 5 --warmup 2 --cpu-sample 0 --no-extra --no-kernel-events > $O/pmc_${tag}_$c.log 2>&1
   done
   rm -rf $O/pmc_${tag}_sq
   rocprofv3 --pmc SQ_BUSY_CU_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU \
-    --kernel-trace --output-format csv -d $O/pmc_${tag}_sq -- python bench.py "$@" --steps 5 --warmup 2 --cpu-sample 0 --no-extra --no-kernel-events > $O/pmc_${tag}_sq.log 2>&1
+    --kernel-trace --output-format csv -d $O/pmc_${tag}_sq -- python bench.py "$@" --full --steps 5 --warmup 2 --cpu-sample 0 --no-extra --no-kernel-events > $O/pmc_${tag}_sq.log 2>&1
 }
 # ---- headline (100k surface scene)
 if [[ $PART == *A* ]]; then
 rm -rf $O/stats
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --cpu-sample 0 --no-extra > $O/bench_stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py --full --cpu-sample 0 --no-extra > $O/bench_stats.log 2>&1
 grep '^{"metric"' $O/bench_stats.log | tail -1 > $O/bench_n1_under_rocprof.json
 python tools/summarize_trace.py "$(ls -t $O/stats/*/*_kernel_trace.csv | head -1)" 15 > $O/bench_n1_trace_summary.txt
 head -14 $O/bench_n1_trace_summary.txt
@@ -38,9 +38,9 @@ fi
 # ---- BASELINE configs[2]: PTv3 semseg on a 120k-point LiDAR-like scan
 if [[ $PART == *B* ]]; then
 A="--model semseg --kind lidar --points 120000"
-python bench.py $A --cpu-sample 0 --no-extra > $O/lidar_bench.json 2> $O/lidar_bench.err
+python bench.py $A --full --cpu-sample 0 --no-extra > $O/lidar_bench.json 2> $O/lidar_bench.err
 rm -rf $O/lidar_stats
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/lidar_stats -- python bench.py $A --cpu-sample 0 --no-extra --steps 5 --warmup 2 --no-kernel-events > $O/lidar_stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/lidar_stats -- python bench.py $A --full --cpu-sample 0 --no-extra --steps 5 --warmup 2 --no-kernel-events > $O/lidar_stats.log 2>&1
 python tools/summarize_trace.py "$(ls -t $O/lidar_stats/*/*_kernel_trace.csv | head -1)" 5 > $O/lidar_trace_summary.txt
 head -10 $O/lidar_trace_summary.txt
 pmc_pair lidar $A
@@ -50,7 +50,7 @@ python tools/pmc_sq.py "$(ls -t $O/pmc_lidar_sq/*/*_counter_collection.csv | hea
 fi
 if [[ $PART == *C* ]]; then
 # ---- the training step: bench line with its roofline + kernel stats of the same command
-python bench.py --mode train --steps 10 --warmup 3 2>/dev/null | grep '^{"metric"' > $O/bench_n1_train.json
+python bench.py --mode train --full --steps 10 --warmup 3 2>/dev/null | grep '^{"metric"' > $O/bench_n1_train.json
 cut -c1-220 $O/bench_n1_train.json
 rm -rf $O/train_stats
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/train_stats -- python bench.py --mode train --steps 5 --warmup 2 --no-kernel-events > $O/train_stats.log 2>&1

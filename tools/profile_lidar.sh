@@ -3,7 +3,7 @@
 # rocprofv3 kernel trace of the same command.  usage (under gpurun): bash tools/profile_lidar.sh r02
 R=${1:-r02}; O=gpurun_out/$R; mkdir -p $O
 export TMPDIR=/tmp
-A="--model semseg --kind lidar --points 120000 --cpu-sample 0 --no-extra"
+A="--model semseg --kind lidar --points 120000 --full --cpu-sample 0 --no-extra"
 python bench.py $A --no-overlap > $O/lidar_bench.json 2> $O/lidar_bench.err
 python bench.py $A --no-kernel-events > $O/lidar_bench_overlap.json 2>> $O/lidar_bench.err
 rm -rf $O/lidar_stats
