@@ -534,6 +534,29 @@ int ptv3_keypoint_aggregate(const float* coord, const float* pred, const int64_t
                             const float* scale, const float* centroid, int mode, float thresh, float* kp_out,
                             int32_t* aux_out, void* stream);
 
+/* ---- global-regression keypoint heads (KeypointPTv3 / KeypointSwin3D) --------------------------------------
+ * ptv3_scene_mean: out (b, c) fp32 = per-scene column mean of feat (n, c) fp32 / bf16, scenes given by the cumulative
+ *   int64 offset (b) - torch_scatter.scatter_mean(feat, point.batch, dim=0) of pointcept/models/keypoint_ptv3.py:44 and
+ *   the per-scene feat[start:end].mean(dim=0) loop of pointcept/models/keypoint_swin3d.py:109-117.  An empty scene
+ *   gives a zero row (scatter_mean).  Accumulates in fp32; deterministic (fixed row chunks that never straddle a scene
+ *   -> fp32 slabs -> per-scene ordered sum, two launches, no atomics); the grid is sized from n and b only (no read of
+ *   offset on the host).  c a multiple of 8 in [8, 1024]; feat, out and workspace 16-byte aligned.
+ * ptv3_scene_mean_head: the same pooling, then the regression head of keypoint_ptv3.py:24-32 / keypoint_swin3d.py:
+ *   30-38 in eval mode on the pooled rows, fp32: out (b, out_dim) = W3 relu(W2 relu((W1 g + b1) s1 + t1) + b2) + b3,
+ *   s1 / t1 = the folded BatchNorm1d, Dropout the identity.  Weights TRANSPOSED: w1t (c, hidden), w2t (hidden, hidden),
+ *   w3t (hidden, out_dim); hidden, out_dim in [1, 1024].  Two launches.
+ * ptv3_scene_mean_bwd: dfeat (n, c) in dtype: dfeat[i] = dg[scene(i)] / n_scene(i) (the backward of the mean; rows
+ *   past offset[b-1] get 0).  workspace: ptv3_scene_mean_workspace_bytes(n, c, b). */
+size_t ptv3_scene_mean_workspace_bytes(int64_t n, int c, int b);
+int ptv3_scene_mean(const void* feat, const int64_t* offset, int64_t n, int c, int b, int dtype, float* out,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int ptv3_scene_mean_head(const void* feat, const int64_t* offset, int64_t n, int c, int b, int dtype, const float* w1t,
+                         const float* b1, const float* s1, const float* t1, int hidden, const float* w2t,
+                         const float* b2, const float* w3t, const float* b3, int out_dim, float* out, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int ptv3_scene_mean_bwd(const float* dg, const int64_t* offset, int64_t n, int c, int b, void* dfeat, int dtype,
+                        void* stream);
+
 /* ---- measurement ---------------------------------------------------------------------------------
  * While enabled, the GEMM / fused-block / attention entry points (forward and backward) bracket their launches with
  * HIP events on the launch stream.  collect() synchronises the device and returns, per kernel family (0 linear,

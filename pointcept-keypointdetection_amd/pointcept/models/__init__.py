@@ -10,3 +10,5 @@ from .point_transformer_v3 import *  # noqa: F401,F403
 from .offset_keypoint_ptv3 import OffsetKeypointPTv3  # noqa: F401
 from .swin3d import Swin3DUNet  # noqa: F401
 from .offset_keypoint_swin3d import OffsetKeypointSwin3D  # noqa: F401
+from .keypoint_ptv3 import KeypointPTv3  # noqa: F401
+from .keypoint_swin3d import KeypointSwin3D  # noqa: F401

@@ -17,6 +17,15 @@ from pointcept.models.utils.hip_layers import Linear, BatchNorm1d
 from .builder import MODELS, build_model
 
 
+def build_coord_feat(backbone, data_dict):
+    """data_dict["coord_feat"] when the batch does not carry one: `coord` + `feat` when the stem expects three more
+    channels than `feat` has, else `feat` (offset_keypoint_swin3d.py:38-56, keypoint_swin3d.py:45-70)."""
+    if "coord_feat" not in data_dict:
+        coord, feat = data_dict["coord"], data_dict["feat"]
+        expected = backbone.stem_layer.conv_layers[0].in_channels
+        data_dict["coord_feat"] = torch.cat([coord, feat], dim=1) if expected == feat.shape[1] + 3 else feat
+
+
 @MODELS.register_module()
 class OffsetKeypointSwin3D(nn.Module):
     def __init__(self, backbone_conf, num_keypoints=6, hidden_dim=256):
@@ -30,10 +39,7 @@ class OffsetKeypointSwin3D(nn.Module):
         self.cls_criterion = nn.BCEWithLogitsLoss(reduction="none")
 
     def forward(self, data_dict):
-        if "coord_feat" not in data_dict:
-            coord, feat = data_dict["coord"], data_dict["feat"]
-            expected = self.backbone.stem_layer.conv_layers[0].in_channels
-            data_dict["coord_feat"] = torch.cat([coord, feat], dim=1) if expected == feat.shape[1] + 3 else feat
+        build_coord_feat(self.backbone, data_dict)
         feat = self.backbone(data_dict)
         x = self.head[1](self.head[0](feat.contiguous()), act=ops.ACT_RELU)
         pred = self.head[3](x).float().view(-1, self.num_keypoints, 4)

@@ -359,6 +359,29 @@ class ClusterGatherFn(Function):
         return ops.segment_sum(dy.contiguous(), order0, seg_start, ctx.n_out), None, None, None
 
 
+class SceneMeanFn(Function):
+    """(B, C) fp32 per-scene column mean of feat (N, C): torch_scatter.scatter_mean(feat, batch, dim=0)
+    (keypoint_ptv3.py:44) / the per-scene mean loop of keypoint_swin3d.py:109-117.  Backward: dfeat[i] =
+    dg[scene(i)] / n_scene(i) in feat's dtype (one launch)."""
+
+    @staticmethod
+    def forward(ctx, feat, offset):
+        feat = feat.contiguous()
+        off = ops._scene_offset(offset, "offset")
+        ctx.save_for_backward(off)
+        ctx.n, ctx.dtype = feat.shape[0], feat.dtype
+        return ops.scene_mean(feat, off)
+
+    @staticmethod
+    def backward(ctx, dg):
+        off, = ctx.saved_tensors
+        return ops.scene_mean_bwd(dg.float().contiguous(), off, ctx.n, ctx.dtype), None
+
+
+def scene_mean(feat, offset):
+    return SceneMeanFn.apply(feat, offset)
+
+
 def linear(x, weight, bias=None):
     return LinearFn.apply(x, weight, bias)
 

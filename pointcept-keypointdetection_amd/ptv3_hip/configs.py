@@ -55,6 +55,16 @@ OFFSET_SWIN3D_CFG = dict(
     ),
 )
 
+# the fork's global-regression models (configs/my_dataset/keypoint_ptv3.py:11-47, keypoint_swin3d.py:11-42)
+KEYPOINT_PTV3_CFG = dict(
+    type="KeypointPTv3", num_keypoints=6,
+    backbone_conf=dict(type="PT-v3m1", **FORK_CFG, pdnorm_bn=False, pdnorm_ln=False, pdnorm_decouple=True,
+                       pdnorm_adaptive=False, pdnorm_affine=True,
+                       pdnorm_conditions=("ScanNet", "S3DIS", "Structured3D")),
+)
+KEYPOINT_SWIN3D_CFG = dict(OFFSET_SWIN3D_CFG, type="KeypointSwin3D",
+                           backbone_conf=dict(OFFSET_SWIN3D_CFG["backbone_conf"]))
+
 # plumbing-size Swin3D: three levels, both head widths the kernel is built for (8 and 16)
 TINY_SWIN3D_CFG = dict(
     type="Swin3D-v1m1", in_channels=9, num_classes=13, base_grid_size=0.02, depths=[2, 2, 2], channels=[16, 32, 32],

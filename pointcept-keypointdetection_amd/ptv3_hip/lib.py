@@ -118,6 +118,11 @@ SIGNATURES = {
     "ptv3_grad_sqnorm": (c_int, [P, c_int, c_int, P, P, P, P, P]),
     "ptv3_grid_hash": (c_int, [P, c_int64, c_double, c_int, P, P, P, P]),
     "ptv3_keypoint_aggregate": (c_int, [P, P, P, c_int, c_int, P, P, c_int, c_float, P, P, P]),
+    "ptv3_scene_mean_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "ptv3_scene_mean": (c_int, [P, P, c_int64, c_int, c_int, c_int, P, P, c_size_t, P]),
+    "ptv3_scene_mean_head": (c_int, [P, P, c_int64, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, c_int, P, P,
+                                     c_size_t, P]),
+    "ptv3_scene_mean_bwd": (c_int, [P, P, c_int64, c_int, c_int, P, c_int, P]),
     "ptv3_profile_enable": (c_int, [c_int]),
     "ptv3_profile_collect": (c_int, [P, P, P, P]),
     "ptv3_profile_hint_flops": (c_int, [ctypes.c_double]),

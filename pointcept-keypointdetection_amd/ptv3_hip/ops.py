@@ -939,6 +939,66 @@ def keypoint_aggregate(coord, pred, offset, mode, scale=None, centroid=None, thr
 
 
 # ---------------------------------------------------------------------------------------------
+# global-regression keypoint heads
+# ---------------------------------------------------------------------------------------------
+def _scene_offset(offset, name):
+    """int32 (tools/KeyPointPrediction_Qt.py:84) or int64 cumulative scene ends -> contiguous int64, on the device."""
+    _chk(offset, name, (torch.int32, torch.int64), 1)
+    return offset if offset.dtype == torch.int64 else offset.long().contiguous()
+
+
+def scene_mean(feat, offset):
+    """(B, C) fp32 per-scene column means of feat (N, C) fp32 / bf16 (scatter_mean; an empty scene gives zeros)."""
+    _chk(feat, "feat", _F, 2)
+    off = _scene_offset(offset, "offset")
+    n, c = feat.shape
+    b = off.shape[0]
+    out = torch.empty((b, c), dtype=torch.float32, device=feat.device)
+    nb = lib.ptv3_scene_mean_workspace_bytes(n, c, b)
+    ws = _ws(nb, feat.device)
+    lib.check(lib.ptv3_scene_mean(_p(feat), _p(off), n, c, b, _dt(feat), _p(out), _p(ws), nb, _stream()),
+              "ptv3_scene_mean")
+    return out
+
+
+def scene_mean_head(feat, offset, w1t, b1, s1, t1, w2t, b2, w3t, b3):
+    """(B, out) fp32: per-scene mean of feat, then W3 relu(W2 relu((W1 g + b1) s1 + t1) + b2) + b3 in fp32 with the
+    TRANSPOSED weights w1t (C, H), w2t (H, H), w3t (H, out) - two launches (ptv3_scene_mean_head)."""
+    _chk(feat, "feat", _F, 2)
+    off = _scene_offset(offset, "offset")
+    for t, nm in ((w1t, "w1t"), (w2t, "w2t"), (w3t, "w3t")):
+        _chk(t, nm, torch.float32, 2)
+    for t, nm in ((b1, "b1"), (s1, "s1"), (t1, "t1"), (b2, "b2"), (b3, "b3")):
+        _chk(t, nm, torch.float32, 1)
+    n, c = feat.shape
+    h, o = w1t.shape[1], w3t.shape[1]
+    if w1t.shape[0] != c or tuple(w2t.shape) != (h, h) or w3t.shape[0] != h or \
+            any(t.shape[0] != h for t in (b1, s1, t1, b2)) or b3.shape[0] != o:
+        raise RuntimeError("scene_mean_head: shape mismatch")
+    b = off.shape[0]
+    out = torch.empty((b, o), dtype=torch.float32, device=feat.device)
+    nb = lib.ptv3_scene_mean_workspace_bytes(n, c, b)
+    ws = _ws(nb, feat.device)
+    lib.check(lib.ptv3_scene_mean_head(_p(feat), _p(off), n, c, b, _dt(feat), _p(w1t), _p(b1), _p(s1), _p(t1), h,
+                                       _p(w2t), _p(b2), _p(w3t), _p(b3), o, _p(out), _p(ws), nb, _stream()),
+              "ptv3_scene_mean_head")
+    return out
+
+
+def scene_mean_bwd(dg, offset, n, dtype):
+    """(n, C) in `dtype`: row i = dg[scene(i)] / n_scene(i), the input gradient of scene_mean."""
+    _chk(dg, "dg", torch.float32, 2)
+    off = _scene_offset(offset, "offset")
+    b, c = dg.shape
+    if off.shape[0] != b:
+        raise RuntimeError("scene_mean_bwd: dg rows != number of scenes")
+    dfeat = torch.empty((n, c), dtype=dtype, device=dg.device)
+    lib.check(lib.ptv3_scene_mean_bwd(_p(dg), _p(off), int(n), c, b, _p(dfeat), _DT[dtype], _stream()),
+              "ptv3_scene_mean_bwd")
+    return dfeat
+
+
+# ---------------------------------------------------------------------------------------------
 # pointops
 # ---------------------------------------------------------------------------------------------
 def knn_query(nsample, xyz, offset, new_xyz, new_offset):
