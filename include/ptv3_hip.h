@@ -557,6 +557,38 @@ int ptv3_scene_mean_head(const void* feat, const int64_t* offset, int64_t n, int
 int ptv3_scene_mean_bwd(const float* dg, const int64_t* offset, int64_t n, int c, int b, void* dfeat, int dtype,
                         void* stream);
 
+/* ---- voting keypoint head (KeypointSwin3DVote) ---------------------------------------------------------------
+ * ptv3_scene_median: out (b, c) fp32, out[s, j] = the LOWER median over the rows i of scene s of x[i, j]
+ *   (+ coord[i, j % 3] when coord (n, 3) is given: one fp32 add inside the kernel, so the (n, K, 3) predicted positions
+ *   of pointcept/models/keypoint_swin3d_plus.py:84 never exist) - the per-scene boolean-mask gather plus
+ *   sample_votes.median(dim=0).values loop of keypoint_swin3d_plus.py:166-189, without its host synchronisations.
+ *   torch.median semantics: rank (rows - 1) / 2 of the ascending order; a NaN in a column gives NaN for that (scene,
+ *   column) only; an empty scene gives zeros (:181-183).  The result is one of the inputs, bit for bit: an exact
+ *   radix select (four 8-bit passes over an order-preserving key; integer histograms merged with integer atomics, every
+ *   hand-off between workgroups a kernel boundary), bitwise reproducible.  x (n, c) fp32 row-major, 1 <= c <= 32, c a
+ *   multiple of 3 with coord; offset (b) cumulative int64, clamped into [0, n]; n < 2^31.  workspace:
+ *   ptv3_scene_median_workspace_bytes(c, b), 16-byte aligned.  One memset + five launches.
+ * ptv3_vote_loss: the training loss and curves of keypoint_swin3d_plus.py:86-164 in two launches.  votes (n, 3k) fp32
+ *   are the head's raw offsets; mask[i, j] = |coord_i - target| < radius; loss = sum over the mask of the xyz mean of
+ *   smooth-L1(beta = 1) of (coord + votes) - target, / max(mask count, 1).  target: (b * k, 3) indexed by the point's
+ *   scene, or with target_per_point (n * k, 3).  scale (optional): (b), or with scale_per_point (n).
+ *   out (2 + k) fp32 = loss, train/masked_dist_err, train/kp{j}_dist_err (masked means of the point-to-target distance
+ *   times scale, 0 where the count is 0); count (1 + k) int32 = mask total, per keypoint.  Fixed row chunks -> slabs ->
+ *   one finishing workgroup (float64 sums, integer counts): no atomics, bitwise reproducible.  1 <= k <= 32.
+ *   workspace: ptv3_vote_loss_workspace_bytes(n, k, b), 16-byte aligned.
+ * ptv3_vote_loss_bwd: autograd of that loss (:111-117): dvotes (n, 3k) = dloss[0] * mask * clamp((coord + votes) -
+ *   target, -1, 1) / (3 * max(count[0], 1)), the mask recomputed; dloss and count stay on the device.  One launch. */
+size_t ptv3_scene_median_workspace_bytes(int c, int b);
+int ptv3_scene_median(const float* x, const float* coord, const int64_t* offset, int64_t n, int c, int b, float* out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+size_t ptv3_vote_loss_workspace_bytes(int64_t n, int k, int b);
+int ptv3_vote_loss(const float* votes, const float* coord, const float* target, int target_per_point,
+                   const int64_t* offset, const float* scale, int scale_per_point, int64_t n, int k, int b, float radius,
+                   float* out, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+int ptv3_vote_loss_bwd(const float* dloss, const float* votes, const float* coord, const float* target,
+                       int target_per_point, const int64_t* offset, const int32_t* count, int64_t n, int k, int b,
+                       float radius, float* dvotes, void* stream);
+
 /* ---- measurement ---------------------------------------------------------------------------------
  * While enabled, the GEMM / fused-block / attention entry points (forward and backward) bracket their launches with
  * HIP events on the launch stream.  collect() synchronises the device and returns, per kernel family (0 linear,

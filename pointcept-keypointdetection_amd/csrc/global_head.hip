@@ -6,6 +6,7 @@
 //   scene_mean_bwd_kernel      dfeat[i, :] = dg[scene(i), :] / n_scene(i)
 // Deterministic: no atomics, and the hand-off between the two halves is a kernel boundary.
 #include "common.h"
+#include "scene_chunks.h"
 #include "../../include/ptv3_hip.h"
 
 namespace ptv3 {
@@ -14,22 +15,6 @@ constexpr int SM_THREADS = 256;     // partial / backward workgroups
 constexpr int SF_THREADS = 1024;    // finishing workgroup (one per scene)
 constexpr int SM_MAX_C = 1024;      // pooled row held in LDS by the finishing kernel
 constexpr int SM_MAX_H = 1024;      // hidden / output width of a head layer
-
-// Rows of scene b, clamped into [0, n]: a malformed offset vector yields wrong numbers, never an access outside feat.
-__device__ __forceinline__ void scene_bounds(const int64_t* __restrict__ offset, int b, int64_t n, int64_t* s,
-                                             int64_t* e) {
-  int64_t lo = b ? offset[b - 1] : 0, hi = offset[b];
-  lo = lo < 0 ? 0 : (lo > n ? n : lo);
-  hi = hi < lo ? lo : (hi > n ? n : hi);
-  *s = lo;
-  *e = hi;
-}
-
-// Chunk ids: the rows are cut at multiples of rb AND at scene boundaries.  Scene b owns the ids
-// [s_b / rb + b, s_b / rb + b + nblk_b) with nblk_b = number of rb-blocks its rows touch; the ids of successive scenes
-// are increasing and disjoint (an empty scene or a scene ending on a multiple of rb leaves one unused id), and every
-// id is < cdiv(n, rb) + B.  So the host sizes the grid from n and B alone; nothing is read back.
-__device__ __forceinline__ int64_t scene_nblk(int64_t s, int64_t e, int64_t rb) { return e > s ? (e - 1) / rb - s / rb + 1 : 0; }
 
 template <typename T>
 __global__ void __launch_bounds__(SM_THREADS) scene_mean_partial_kernel(const T* __restrict__ x,
@@ -40,18 +25,7 @@ __global__ void __launch_bounds__(SM_THREADS) scene_mean_partial_kernel(const T*
   typedef float VF __attribute__((ext_vector_type(VE)));
   __shared__ float red[SM_THREADS * VE];
   const int64_t j = blockIdx.x;
-  // scene of this chunk = #{b >= 1 : first id of b <= j} (the first ids increase with b)
-  int b = 0;
-  for (int b0 = 0; b0 < nb; b0 += SM_THREADS) {
-    const int q = b0 + (int)threadIdx.x;
-    int hit = 0;
-    if (q >= 1 && q < nb) {
-      int64_t s, e;
-      scene_bounds(offset, q, n, &s, &e);
-      hit = s / rb + q <= j;
-    }
-    b += __syncthreads_count(hit);
-  }
+  const int b = scene_of_chunk<SM_THREADS>(offset, nb, n, rb, j);
   int64_t s, e;
   scene_bounds(offset, b, n, &s, &e);
   const int64_t blk = j - b;

@@ -382,6 +382,35 @@ def scene_mean(feat, offset):
     return SceneMeanFn.apply(feat, offset)
 
 
+class VoteLossFn(Function):
+    """The vote loss of keypoint_swin3d_plus.py:86-164 on the head's raw votes (N, 3K): forward = the two launches of
+    ops.vote_loss -> (loss, curves (1 + K), mask count (1 + K) int32), backward = one launch (the mask is recomputed).
+    Only the loss carries a gradient; curves and count are marked non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, votes, coord, target, offset, vote_radius, scale):
+        votes = votes.contiguous()
+        coord, target = coord.contiguous(), target.contiguous()
+        off = ops._scene_offset(offset, "offset")
+        out, count = ops.vote_loss(votes, coord, target, off, vote_radius, None if scale is None else scale.contiguous())
+        ctx.save_for_backward(votes, coord, target, off, count)
+        ctx.vote_radius = vote_radius
+        loss, curves = out[0], out[1:]
+        ctx.mark_non_differentiable(curves, count)
+        return loss, curves, count
+
+    @staticmethod
+    def backward(ctx, dloss, _dcurves, _dcount):
+        votes, coord, target, off, count = ctx.saved_tensors
+        dvotes = ops.vote_loss_bwd(dloss.float().contiguous(), votes, coord, target, off, count, ctx.vote_radius)
+        return dvotes, None, None, None, None, None
+
+
+def vote_loss(votes, coord, target, offset, vote_radius, scale=None):
+    """-> (loss 0-d with grad, curves (1 + K) detached: masked_dist_err then kp{k}_dist_err, count (1 + K) int32)."""
+    return VoteLossFn.apply(votes, coord, target, offset, vote_radius, scale)
+
+
 def linear(x, weight, bias=None):
     return LinearFn.apply(x, weight, bias)
 

@@ -64,6 +64,9 @@ KEYPOINT_PTV3_CFG = dict(
 )
 KEYPOINT_SWIN3D_CFG = dict(OFFSET_SWIN3D_CFG, type="KeypointSwin3D",
                            backbone_conf=dict(OFFSET_SWIN3D_CFG["backbone_conf"]))
+# the fork's voting model (configs/my_dataset/keypoint_swin3d_plus.py:14-52)
+KEYPOINT_SWIN3D_VOTE_CFG = dict(OFFSET_SWIN3D_CFG, type="KeypointSwin3DVote", vote_radius=0.3,
+                                backbone_conf=dict(OFFSET_SWIN3D_CFG["backbone_conf"]))
 
 # plumbing-size Swin3D: three levels, both head widths the kernel is built for (8 and 16)
 TINY_SWIN3D_CFG = dict(

@@ -123,6 +123,11 @@ SIGNATURES = {
     "ptv3_scene_mean_head": (c_int, [P, P, c_int64, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, c_int, P, P,
                                      c_size_t, P]),
     "ptv3_scene_mean_bwd": (c_int, [P, P, c_int64, c_int, c_int, P, c_int, P]),
+    "ptv3_scene_median_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ptv3_scene_median": (c_int, [P, P, P, c_int64, c_int, c_int, P, P, c_size_t, P]),
+    "ptv3_vote_loss_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "ptv3_vote_loss": (c_int, [P, P, P, c_int, P, P, c_int, c_int64, c_int, c_int, c_float, P, P, P, c_size_t, P]),
+    "ptv3_vote_loss_bwd": (c_int, [P, P, P, P, c_int, P, P, c_int64, c_int, c_int, c_float, P, P]),
     "ptv3_profile_enable": (c_int, [c_int]),
     "ptv3_profile_collect": (c_int, [P, P, P, P]),
     "ptv3_profile_hint_flops": (c_int, [ctypes.c_double]),

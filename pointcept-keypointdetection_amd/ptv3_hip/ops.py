@@ -999,6 +999,84 @@ def scene_mean_bwd(dg, offset, n, dtype):
 
 
 # ---------------------------------------------------------------------------------------------
+# voting keypoint head
+# ---------------------------------------------------------------------------------------------
+def scene_median(x, coord, offset):
+    """(B, C) fp32: the lower median over each scene's rows of x (N, C) fp32 (+ coord[:, j % 3] when coord (N, 3) is
+    given) - torch.median(dim=0).values per scene (keypoint_swin3d_plus.py:166-189): NaN in a column gives NaN there, an
+    empty scene zeros.  An exact selection, bitwise reproducible; B = len(offset), nothing is read back."""
+    _chk(x, "x", torch.float32, 2)
+    _chk(coord, "coord", torch.float32, 2)
+    off = _scene_offset(offset, "offset")
+    n, c = x.shape
+    if coord is not None and tuple(coord.shape) != (n, 3):
+        raise RuntimeError(f"scene_median: coord {tuple(coord.shape)}, expected ({n}, 3)")
+    b = off.shape[0]
+    out = torch.empty((b, c), dtype=torch.float32, device=x.device)
+    nb = lib.ptv3_scene_median_workspace_bytes(c, b)
+    ws = _ws(nb, x.device)
+    lib.check(lib.ptv3_scene_median(_p(x), _p(coord), _p(off), n, c, b, _p(out), _p(ws), nb, _stream()),
+              "ptv3_scene_median")
+    return out
+
+
+def _vote_target(target, n, k, b):
+    """The reference's target layouts (keypoint_swin3d_plus.py:95-102), decided from host shapes: B * K * 3 numbers are
+    per-scene rows, N leading rows are per-point rows; anything else is its ValueError.  -> (target (rows, 3), flag)"""
+    if target.numel() == b * k * 3:
+        return target.reshape(b * k, 3), 0
+    if target.shape[0] == n and target.numel() == n * k * 3:
+        return target.reshape(n * k, 3), 1
+    raise ValueError("Target shape mismatch.")
+
+
+def _vote_args(votes, coord, target, offset):
+    _chk(votes, "votes", torch.float32, 2)
+    _chk(coord, "coord", torch.float32, 2)
+    _chk(target, "target", torch.float32)
+    off = _scene_offset(offset, "offset")
+    n = votes.shape[0]
+    if votes.shape[1] % 3 or tuple(coord.shape) != (n, 3):
+        raise RuntimeError(f"vote_loss: votes {tuple(votes.shape)} / coord {tuple(coord.shape)}: expected (N, 3K), (N, 3)")
+    k, b = votes.shape[1] // 3, off.shape[0]
+    tgt, per_point = _vote_target(target, n, k, b)
+    return off, n, k, b, tgt, per_point
+
+
+def vote_loss(votes, coord, target, offset, vote_radius, scale=None):
+    """The vote loss and curves of keypoint_swin3d_plus.py:86-164 in two launches -> (out (2 + K) fp32 = loss,
+    train/masked_dist_err, train/kp{k}_dist_err; count (1 + K) int32 = mask total, per keypoint).  votes (N, 3K) are the
+    raw offsets; target (B * K, 3) / (B, K, 3) by scene or (N, K, 3) by point; scale (B) / (N), optionally (., 1)."""
+    off, n, k, b, tgt, per_point = _vote_args(votes, coord, target, offset)
+    scale_pp = 0
+    if scale is not None:
+        _chk(scale, "scale", torch.float32)
+        scale_pp = int(scale.shape[0] == n)          # :127-128: anything not N long is indexed by the scene
+        if scale.numel() != (n if scale_pp else b):
+            raise RuntimeError(f"vote_loss: scale {tuple(scale.shape)}: expected one value per scene or per point")
+    out = torch.empty(2 + k, dtype=torch.float32, device=votes.device)
+    count = torch.empty(1 + k, dtype=torch.int32, device=votes.device)
+    nbytes = lib.ptv3_vote_loss_workspace_bytes(n, k, b)
+    ws = _ws(nbytes, votes.device)
+    lib.check(lib.ptv3_vote_loss(_p(votes), _p(coord), _p(tgt), per_point, _p(off), _p(scale), scale_pp, n, k, b,
+                                 float(vote_radius), _p(out), _p(count), _p(ws), nbytes, _stream()), "ptv3_vote_loss")
+    return out, count
+
+
+def vote_loss_bwd(dloss, votes, coord, target, offset, count, vote_radius):
+    """dvotes (N, 3K) fp32 of vote_loss: dloss * mask * clamp((coord + votes) - target, -1, 1) / (3 max(count, 1))."""
+    off, n, k, b, tgt, per_point = _vote_args(votes, coord, target, offset)
+    _chk(dloss, "dloss", torch.float32)
+    _chk(count, "count", torch.int32, 1)
+    if dloss.numel() != 1 or count.shape[0] != 1 + k:
+        raise RuntimeError("vote_loss_bwd: dloss must hold one value and count 1 + K")
+    dvotes = torch.empty_like(votes)
+    lib.check(lib.ptv3_vote_loss_bwd(_p(dloss), _p(votes), _p(coord), _p(tgt), per_point, _p(off), _p(count), n, k, b,
+                                     float(vote_radius), _p(dvotes), _stream()), "ptv3_vote_loss_bwd")
+    return dvotes
+
+
+# ---------------------------------------------------------------------------------------------
 # pointops
 # ---------------------------------------------------------------------------------------------
 def knn_query(nsample, xyz, offset, new_xyz, new_offset):
