@@ -464,10 +464,14 @@ def _crse_attention_torch(q, k, v, qt, kt, vt, offs, w_sizes, w2n, n2n, cr):
                                                      (2, 16, 5, 50, "XYZ_RGB"), (2, 32, 5, 4, "XYZ")])
 def test_crse_attention_backward_vs_torch_autograd(dev, heads, hd, ws, quant, crse):
     """ptv3_swin_attn_bwd: dq, dk, dv and the three table gradients against torch autograd (float64) over the restated
-    forward, relative L2 <= 1e-4 each.  The fork's training config (quant 50, XYZ_RGB, head_dim 16) is one of the cases."""
+    forward, relative L2 <= 1e-4 each.  The fork's table setting (quant 50, XYZ_RGB, head_dim 16) is one of the cases,
+    on sheet-like scenes whose windows hold 1 .. 58 tokens: one key per lane, one step of the gradient sweep.  Windows
+    above 64 tokens (the fork's 7^3 windows on its coarse levels), bf16 and per-row checks of the table gradients are
+    test_hip_swin3d_windows.py's."""
     from ptv3_hip import autograd as A
     coords = _surface(1500, 40, heads + hd + ws)
     q, k, v, tabs, offs, w_sizes, w2n, n2n, cr = _case(coords, heads, hd, ws, quant, crse, seed=3, table_std=0.3)
+    assert w_sizes.min() < 16 < w_sizes.max() <= 64
     rng = np.random.default_rng(1)
     dout = rng.normal(size=q.shape).astype(np.float32)
     ref_in = [torch.from_numpy(a).double().requires_grad_(True) for a in (q, k, v, *tabs)]
