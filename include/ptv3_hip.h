@@ -673,6 +673,40 @@ int ptv3_interpolation_forward(int n, int c, int k, const float* input, const in
                                const float* weight, float* output, void* stream);
 int ptv3_interpolation_backward(int n, int c, int k, const float* grad_output, const int* idx,
                                 const float* weight, float* grad_input, void* stream);
+/* Farthest point sampling, replacing libs/pointops/src/sampling/sampling_cuda_kernel.cu:15-129 (same arguments as its
+ * launcher, plus the stream).  xyz (n,3) fp32; offset / new_offset (b) int32 cumulative ends of the scenes and of their
+ * samples; idx (new_offset[b-1]) int32 receives GLOBAL row indices.  Every scene starts at its first point and then
+ * repeatedly takes the point whose running minimum squared distance (dx*dx + dy*dy + dz*dz in fp32) to the chosen set is
+ * largest.  tmp (n) fp32 is in/out: read as the initial running distances (non-negative; the caller fills it with
+ * 1e10), it holds the final ones on return.  One workgroup per scene; n_max (the largest scene) only selects where a
+ * scene's state lives (registers up to 16384 points, then 8192 more in LDS, then global memory).  Bitwise reproducible.
+ * Two deliberate differences from the reference:
+ *   - ties go to the LOWEST index (the reference's tie order depends on its block size), so a scene of identical
+ *     points returns its first index repeated;
+ *   - a scene asked for zero samples writes nothing (the reference writes idx[start_m] regardless, which lands in the
+ *     next scene's slot or past the end). */
+int ptv3_farthest_point_sampling(int b, int n_max, const float* xyz, const int* offset, const int* new_offset,
+                                 float* tmp, int* idx, void* stream);
+
+/* ---- Point Transformer V1 vector attention, eval forward ------------------------------------------
+ * PointTransformerLayer.forward after its three input projections (pointcept/models/point_transformer/
+ * point_transformer_seg.py:90-120) in one launch.  x_q / x_k / x_v (n,c) fp32, xyz (n,3) fp32, idx (n,ns) int32 rows of
+ * the point's neighbours (-1, or anything outside [0,n), = missing: zero feature rows and a zero offset, as
+ * pointops.grouping gives them), out (n,c) fp32.  With j = idx[i,s], cs = c/8 and every BatchNorm folded to a per-channel
+ * (scale s, shift t) that also carries the bias of the Linear in front of it:
+ *   h   = relu(s_p * (w_p1 (xyz[j] - xyz[i])) + t_p)                     w_p1 (3,3), s_p / t_p (3)
+ *   p_r = w_p2 h + b_p2                                                  w_p2 (c,3), b_p2 (c)
+ *   a   = relu(s_c * (x_k[j] - x_q[i] + p_r) + t_c)                      s_c / t_c (c)
+ *   w   = w_w2 relu(s_w * (w_w1 a) + t_w) + b_w2                         w_w1 (cs,c), s_w / t_w (cs), w_w2 (cs,cs), b_w2 (cs)
+ *   w   = softmax over the ns neighbours, per channel of w
+ *   out[i, g*cs + t] = sum_s (x_v[j, g*cs + t] + p_r[g*cs + t]) * w[s, t]   for the 8 share groups g
+ * c: a multiple of 8 in [8,512]; ns in [1,32]; anything else is refused with PTV3_ERR_ARG before any launch.  fp32
+ * arithmetic and accumulation, no atomics: bitwise reproducible. */
+int ptv3_vector_attn_fwd(const float* x_q, const float* x_k, const float* x_v, const float* xyz, const int32_t* idx,
+                         int64_t n, int c, int ns, const float* w_p1, const float* s_p, const float* t_p,
+                         const float* w_p2, const float* b_p2, const float* s_c, const float* t_c, const float* w_w1,
+                         const float* s_w, const float* t_w, const float* w_w2, const float* b_w2, float* out,
+                         void* stream);
 
 #ifdef __cplusplus
 }

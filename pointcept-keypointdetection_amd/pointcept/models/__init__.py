@@ -13,3 +13,4 @@ from .offset_keypoint_swin3d import OffsetKeypointSwin3D  # noqa: F401
 from .keypoint_ptv3 import KeypointPTv3  # noqa: F401
 from .keypoint_swin3d import KeypointSwin3D  # noqa: F401
 from .keypoint_swin3d_vote import KeypointSwin3DVote  # noqa: F401
+from .keypoint_ptv1 import KeypointPTv1  # noqa: F401

@@ -43,3 +43,10 @@ def interpolation_backward_cuda(n, c, k, grad_output, idx, weight, grad_input):
     lib.check(lib.ptv3_interpolation_backward(n, c, k, _p(grad_output, torch.float32), _p(idx, torch.int32),
                                               _p(weight, torch.float32), _p(grad_input, torch.float32), _s()),
               "interpolation_backward")
+
+
+def farthest_point_sampling_cuda(b, n_max, xyz, offset, new_offset, tmp, idx):
+    """sampling_cuda.cpp's signature: tmp (n) fp32 in/out (initial / final running distances), idx int32 out."""
+    lib.check(lib.ptv3_farthest_point_sampling(int(b), int(n_max), _p(xyz, torch.float32), _p(offset, torch.int32),
+                                               _p(new_offset, torch.int32), _p(tmp, torch.float32),
+                                               _p(idx, torch.int32), _s()), "farthest_point_sampling")

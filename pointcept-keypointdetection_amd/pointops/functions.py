@@ -9,6 +9,7 @@ hooks/evaluator.py:569-575, the PTv2 / Sonata model files):
     interpolation(xyz, new_xyz, feat, offset, new_offset, k=3)   inverse-distance blend of the k nearest rows
     interpolation2(...)                                           same arguments
     knn_query_and_group(...), offset2batch, batch2offset
+    farthest_point_sampling(xyz, offset, new_offset)              int32 global row indices of the samples, scene by scene
 
 Both spellings of grouping / interpolation run the same HIP kernels here (the reference keeps a torch-indexing and
 a CUDA variant of each); gradients with respect to the features flow through the matching backward kernels.
@@ -51,6 +52,24 @@ def knn_query(nsample, xyz, offset, new_xyz=None, new_offset=None, cell=None):
     dist2 = torch.zeros((m, nsample), dtype=torch.float32, device=xyz.device)
     _C.knn_query_cuda(m, nsample, xyz, new_xyz, _i32(offset), _i32(new_offset), idx, dist2)
     return idx, dist2.sqrt_()
+
+
+@torch.no_grad()
+def farthest_point_sampling(xyz, offset, new_offset):
+    """libs/pointops/functions/sampling.py:7-27: new_offset[i] - new_offset[i-1] samples of scene i, starting at its
+    first point, each the point farthest from those already taken; idx (new_offset[-1]) int32 rows of xyz.  int32 or
+    int64 offsets.  Ties go to the lowest index and a scene asked for nothing takes nothing (ptv3_farthest_point_sampling).
+    One host read of the offsets (the reference reads them entry by entry); no gradient."""
+    from ptv3_hip import ops
+    for t, nm in ((xyz, "xyz"), (offset, "offset"), (new_offset, "new_offset")):
+        if not t.is_cuda:
+            raise RuntimeError(f"farthest_point_sampling: {nm}: expected a GPU tensor (no CPU fallback)")
+    if not xyz.is_contiguous():
+        raise AssertionError("farthest_point_sampling: xyz must be contiguous")
+    if offset.shape != new_offset.shape or offset.dim() != 1:
+        raise ValueError("farthest_point_sampling: offset / new_offset must be 1-d and of one length")
+    ends = torch.stack([offset.long(), new_offset.long()]).tolist()
+    return ops.farthest_point_sampling(xyz, _i32(offset), _i32(new_offset), ends[0], ends[1])
 
 
 class _RowGather(torch.autograd.Function):

@@ -67,6 +67,8 @@ KEYPOINT_SWIN3D_CFG = dict(OFFSET_SWIN3D_CFG, type="KeypointSwin3D",
 # the fork's voting model (configs/my_dataset/keypoint_swin3d_plus.py:14-52)
 KEYPOINT_SWIN3D_VOTE_CFG = dict(OFFSET_SWIN3D_CFG, type="KeypointSwin3DVote", vote_radius=0.3,
                                 backbone_conf=dict(OFFSET_SWIN3D_CFG["backbone_conf"]))
+# the fork's Point Transformer V1 regression model (configs/my_dataset/keypoint_ptv1.py:20-28)
+KEYPOINT_PTV1_CFG = dict(type="KeypointPTv1-50", in_channels=7, num_keypoints=6, hidden_dim=256)
 
 # plumbing-size Swin3D: three levels, both head widths the kernel is built for (8 and 16)
 TINY_SWIN3D_CFG = dict(

@@ -144,6 +144,8 @@ SIGNATURES = {
     "ptv3_grouping_backward": (c_int, [c_int, c_int, c_int, P, P, P, P]),
     "ptv3_interpolation_forward": (c_int, [c_int, c_int, c_int, P, P, P, P, P]),
     "ptv3_interpolation_backward": (c_int, [c_int, c_int, c_int, P, P, P, P, P]),
+    "ptv3_farthest_point_sampling": (c_int, [c_int, c_int, P, P, P, P, P, P]),
+    "ptv3_vector_attn_fwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
 }
 
 

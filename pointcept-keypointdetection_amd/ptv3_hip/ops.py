@@ -1093,6 +1093,71 @@ def knn_query(nsample, xyz, offset, new_xyz, new_offset):
     return idx, dist2
 
 
+# where ptv3_farthest_point_sampling keeps a scene's coordinates and running distances: registers up to FPS_REG_POINTS
+# points, LDS for the next FPS_LDS_POINTS, global memory beyond (csrc/fps.hip)
+FPS_REG_POINTS = 16384
+FPS_LDS_POINTS = 8192
+
+
+def farthest_point_sampling(xyz, offset, new_offset, ends_host, new_ends_host):
+    """idx (m) int32 global rows: farthest point sampling of every scene (ptv3_farthest_point_sampling).  offset /
+    new_offset (b) int32 on the device, ends_host / new_ends_host the same numbers as Python lists (the caller has
+    them: nothing is read back here); they are checked against the tensors' sizes before any launch."""
+    _chk(xyz, "xyz", torch.float32, 2)
+    _chk(offset, "offset", torch.int32, 1)
+    _chk(new_offset, "new_offset", torch.int32, 1)
+    n, b = xyz.shape[0], offset.shape[0]
+    if xyz.shape[1] != 3 or new_offset.shape[0] != b or len(ends_host) != b or len(new_ends_host) != b:
+        raise ValueError("farthest_point_sampling: xyz must be (n, 3) and the four offset lists of one length")
+    sizes = [e - s for s, e in zip([0] + list(ends_host[:-1]), ends_host)]
+    counts = [e - s for s, e in zip([0] + list(new_ends_host[:-1]), new_ends_host)]
+    if b and (ends_host[-1] != n or min(sizes) < 0 or min(counts) < 0):
+        raise ValueError(f"farthest_point_sampling: offsets {list(ends_host)} / {list(new_ends_host)} do not describe "
+                         f"{n} points")
+    if any(c > 0 and s == 0 for s, c in zip(sizes, counts)):
+        raise ValueError("farthest_point_sampling: samples asked of an empty scene")
+    if b == 0:    # no scene, nothing to take (the C entry wants at least one)
+        if n:
+            raise ValueError(f"farthest_point_sampling: {n} points but no scene")
+        return torch.zeros(0, dtype=torch.int32, device=xyz.device)
+    idx = torch.zeros(new_ends_host[-1], dtype=torch.int32, device=xyz.device)
+    tmp = torch.full((n,), 1e10, dtype=torch.float32, device=xyz.device)
+    lib.check(lib.ptv3_farthest_point_sampling(b, max(sizes), _p(xyz), _p(offset), _p(new_offset), _p(tmp),
+                                               _p(idx), _stream()), "ptv3_farthest_point_sampling")
+    return idx
+
+
+def fold_batchnorm(bn, bias=None):
+    """eval BatchNorm1d (or LayerNorm1d) -> per-channel fp32 (scale, shift) from its running statistics; `bias`, the bias
+    of the Linear in front of it, is carried into the shift: bn(x + bias) = scale * x + shift."""
+    scale = bn.weight.detach().float() * torch.rsqrt(bn.running_var.float() + bn.eps)
+    mean = bn.running_mean.float() if bias is None else bn.running_mean.float() - bias.detach().float()
+    return scale.contiguous(), (bn.bias.detach().float() - mean * scale).contiguous()
+
+
+def vector_attention(x_q, x_k, x_v, xyz, idx, w_p1, s_p, t_p, w_p2, b_p2, s_c, t_c, w_w1, s_w, t_w, w_w2, b_w2):
+    """out (n, c) fp32: the Point Transformer V1 vector attention over the neighbour rows idx (n, ns) int32 (-1 =
+    missing), BatchNorms folded (fold_batchnorm); formulas and weight shapes: ptv3_vector_attn_fwd in
+    include/ptv3_hip.h."""
+    for t, nm in ((x_q, "x_q"), (x_k, "x_k"), (x_v, "x_v"), (xyz, "xyz")):
+        _chk(t, nm, torch.float32, 2)
+    _chk(idx, "idx", torch.int32, 2)
+    n, c = x_q.shape
+    ns, cs = idx.shape[1], c // 8
+    if x_k.shape != x_q.shape or x_v.shape != x_q.shape or tuple(xyz.shape) != (n, 3) or idx.shape[0] != n:
+        raise RuntimeError("vector_attention: x_q / x_k / x_v (n, c), xyz (n, 3) and idx (n, ns) disagree")
+    shapes = ((w_p1, (3, 3)), (s_p, (3,)), (t_p, (3,)), (w_p2, (c, 3)), (b_p2, (c,)), (s_c, (c,)), (t_c, (c,)),
+              (w_w1, (cs, c)), (s_w, (cs,)), (t_w, (cs,)), (w_w2, (cs, cs)), (b_w2, (cs,)))
+    for k, (t, shape) in enumerate(shapes):
+        _chk(t, f"vector_attention weight {k}", torch.float32)
+        if c % 8 == 0 and tuple(t.shape) != shape:
+            raise RuntimeError(f"vector_attention: weight {k} has shape {tuple(t.shape)}, expected {shape}")
+    out = torch.empty_like(x_q)
+    lib.check(lib.ptv3_vector_attn_fwd(_p(x_q), _p(x_k), _p(x_v), _p(xyz), _p(idx), n, c, ns,
+                                       *[_p(t) for t, _ in shapes], _p(out), _stream()), "ptv3_vector_attn_fwd")
+    return out
+
+
 def _scene_ids(offset, n):
     counts = torch.diff(offset.long(), prepend=offset.new_zeros(1).long())
     return torch.repeat_interleave(torch.arange(offset.shape[0], device=offset.device), counts, output_size=n)
