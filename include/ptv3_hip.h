@@ -230,7 +230,9 @@ int ptv3_cast(const void* x, int src_dtype, void* y, int dst_dtype, int64_t coun
  *         caller reads it back (the one host sync per pooling, as torch.unique has).
  *         batch (n) int64 + pooled_offset (b) int64 (both optional): cumulative scene ends of the
  *         pooled Point (= batch2offset(batch[head]), models/utils/misc.py:32-34); pooled_offset[b-1]
- *         equals n_out.  workspace: ptv3_pool_workspace_bytes(n). */
+ *         equals n_out.  Each entry is written from its scene's last point: a scene WITHOUT points
+ *         keeps what the caller put there (ops.pool_segments pre-fills -1 and forward-fills on the
+ *         host; ptv3_forward refuses empty scenes).  workspace: ptv3_pool_workspace_bytes(n). */
 size_t ptv3_pool_workspace_bytes(int64_t n);
 int ptv3_pool_segments(const int64_t* code0, const int64_t* order0, int64_t n, int shift_bits,
                        const int64_t* batch, int64_t* cluster, int32_t* seg_start, int32_t* n_out,

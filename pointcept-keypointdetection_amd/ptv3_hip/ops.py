@@ -534,12 +534,14 @@ def cast(x, dtype):
 # ---------------------------------------------------------------------------------------------
 def pool_segments(code0, order0, shift_bits, batch=None, num_scenes=0):
     """cluster (n) int64, seg_start (n_out+1) int32, n_out (python int; ONE host sync, as torch.unique).
-    With batch: also the pooled Point's cumulative offsets, returned as (device tensor, host list)."""
+    With batch: also the pooled Point's cumulative offsets, returned as (device tensor, host list); a scene
+    without points repeats its predecessor's offset (0 for a leading one)."""
     _chk(code0, "code0", torch.int64, 1)
     _chk(order0, "order0", torch.int64, 1)
     _chk(batch, "batch", torch.int64, 1)
     n = code0.shape[0]
-    pooled_offset = torch.empty(num_scenes, dtype=torch.int64, device=code0.device) if batch is not None else None
+    # the kernel writes a scene's entry from that scene's last point, so a scene without points keeps the -1
+    pooled_offset = torch.full((num_scenes,), -1, dtype=torch.int64, device=code0.device) if batch is not None else None
     cluster = torch.empty(n, dtype=torch.int64, device=code0.device)
     seg_start = torch.empty(n + 1, dtype=torch.int32, device=code0.device)
     n_out = torch.empty(1, dtype=torch.int32, device=code0.device)
@@ -550,6 +552,11 @@ def pool_segments(code0, order0, shift_bits, batch=None, num_scenes=0):
               "ptv3_pool_segments")
     if batch is not None:
         host = [int(v) for v in pooled_offset.tolist()]  # the one sync; n_out is the last entry
+        if min(host) < 0:  # empty scenes (rare): forward-fill on the host, then rewrite the device copy
+            for b, v in enumerate(host):
+                if v < 0:
+                    host[b] = host[b - 1] if b else 0
+            pooled_offset.copy_(torch.tensor(host, dtype=torch.int64))
         return cluster, seg_start[:host[-1] + 1], host[-1], pooled_offset, host
     cnt = int(n_out.item())
     return cluster, seg_start[:cnt + 1], cnt
