@@ -710,6 +710,60 @@ int ptv3_vector_attn_fwd(const float* x_q, const float* x_k, const float* x_v, c
                          const float* s_w, const float* t_w, const float* w_w2, const float* b_w2, float* out,
                          void* stream);
 
+/* ---- OA-CNNs: kernel-2 / stride-2 sparse convolution pair (fp32) -----------------------------------
+ * spconv.SparseConv3d(kernel_size=2, stride=2) of DonwBlock.down and spconv.SparseInverseConv3d of UpBlock.up
+ * (pointcept/models/oacnns/oacnns_v1m1_base.py:130-141, 184-194; parity with the spconv wheel unpinned).  A fine site
+ * (b, x, y, z) has ONE parent (b, x>>1, y>>1, z>>1), reached through tap (x&1)*4 + (y&1)*2 + (z&1); a site whose
+ * parent lies outside the coarse shape (sx, sy, sz) has none.
+ * plan, step 1: key[i] = ((b*sx + px)*sy + py)*sz + pz, or none_key (> every parent key, so it sorts last) for a
+ *   site without a parent; tap[i] (n) int32.  The caller then sorts the keys (ptv3_argsort_i64) and ranks them
+ *   (ptv3_pool_segments, shift 0).
+ * plan, step 2: from rank / order / seg_start / n_out of those two calls: parent (n) int32 (-1 = none), child
+ *   (>= coarse rows, 8) int32 pre-filled with -1 by the caller, coarse (>= coarse rows, 4) int32 sites in (b, x, y, z)
+ *   order, up_key (n) int64 = tap, or 8 without a parent (sorted by the caller into up_rows), counts (10) int32
+ *   pre-zeroed: [0] coarse rows, [1 + t] sites of tap t, [9] sites without a parent - the ONE host read of a level. */
+int ptv3_down2_keys(const int32_t* indices, int64_t n, int sx, int sy, int sz, int64_t none_key, int64_t* key,
+                    int32_t* tap, void* stream);
+int ptv3_down2_children(const int32_t* indices, const int64_t* key, const int32_t* tap, const int64_t* rank,
+                        const int64_t* order, const int32_t* seg_start, const int32_t* n_out, int64_t n,
+                        int64_t none_key, int32_t* parent, int32_t* child, int32_t* coarse, int64_t* up_key,
+                        int32_t* counts, void* stream);
+/* down (:130-141): out[j] = epi(sum_t w[:, t, :] x[child[j][t]]), x (n_in, cin), w (cout, 8, cin), out (m_out, cout);
+ * up (:184-194):   out[i] = epi(w[:, tap(i), :] y[parent[i]]), y (m_in, cin), out (n, cout); rows without a parent get
+ *   epi(0).  up_rows (n) int32: the rows stably sorted by up_key; tap_start_host: 10 host ints, rows
+ *   [tap_start[t], tap_start[t+1]) of up_rows use tap t (t = 8: no parent) - a row costs one tap of multiply work.
+ * epi = * bn_scale + bn_shift (optional, together), then act (PTV3_ACT_NONE | PTV3_ACT_RELU).  cin % 4 == 0. */
+int ptv3_down2_conv(const float* x, const float* w, const int32_t* child, int64_t n_in, int64_t m_out, int cin, int cout,
+                    const float* bn_scale, const float* bn_shift, int act, float* out, void* stream);
+int ptv3_up2_conv(const float* y, const float* w, const int32_t* parent, const int32_t* up_rows,
+                  const int32_t* tap_start_host, int64_t n, int64_t m_in, int cin, int cout, const float* bn_scale,
+                  const float* bn_shift, int act, float* out, void* stream);
+
+/* ---- OA-CNNs: adaptive aggregator of BasicBlock.forward (oacnns_v1m1_base.py:87-110, fp32) -------------
+ * Partition (DonwBlock.forward :158-164, torch_geometric voxel_grid + torch.unique): key[i] packs
+ * (b, (x - min_x) / g, (y - min_y) / g, (z - min_z) / g) with min_xyz (3) int32 ON THE DEVICE (the minimum over all
+ * rows of the batch) and 1 <= g <= 128; ptv3_argsort_i64 + ptv3_pool_segments turn it into order / seg_start /
+ * cluster ids, and the cluster count stays on the device (n_clusters): every kernel below is launched for m rows.
+ *   center (:92):       out[i] = x[i] - mean over i's cluster of x                          x (m, C) row stride ldx
+ *   softmax_sum (:94-97): agg[k] = sum_{i in k} v[i] e[i] / (sum_{i in k} e[i] + 1e-6), e = exp(p - *global_max)
+ *                       p, v (m, C) with row strides ldp, ldv; agg (>= clusters, C)
+ *   mix (:99-102):      out[i, out_col : out_col + C] = sum_l softmax(logits[i, :L])[l] * agg_l[cluster_l[i]], L <= 4
+ *                       agg_host / cluster_host: L host arrays of device pointers; head (optional, (m, C) stride ldh)
+ *                       is copied to out[i, 0:C] (the left half of the `fuse` input, :103-104); out row stride ldo
+ * C a multiple of 4 in [4, 512]; fp32 accumulation in a fixed order, no atomics: bitwise reproducible; clusters of 1
+ * to m rows.  Anything else is refused with PTV3_ERR_ARG before a launch. */
+int ptv3_cluster_keys(const int32_t* indices, int64_t m, const int32_t* min_xyz, int g, int64_t* key, void* stream);
+int ptv3_cluster_center(const float* x, int64_t ldx, const int64_t* order, const int32_t* seg_start,
+                        const int32_t* n_clusters, int64_t m, int c, float* out, void* stream);
+int ptv3_cluster_softmax_sum(const float* p, int64_t ldp, const float* v, int64_t ldv, const float* global_max,
+                             const int64_t* order, const int32_t* seg_start, const int32_t* n_clusters, int64_t m,
+                             int c, float* agg, void* stream);
+int ptv3_cluster_mix(const float* logits, int64_t ldl, const float* const* agg_host, const int64_t* const* cluster_host,
+                     int levels, const float* head, int64_t ldh, int64_t m, int c, float* out, int64_t ldo, int out_col,
+                     void* stream);
+/* out = act(a + b) over `count` fp32 values (count % 4 == 0): the block's closing relu(x + res) (:109) */
+int ptv3_add_act(const float* a, const float* b, int act, float* out, int64_t count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,3 +14,5 @@ from .keypoint_ptv3 import KeypointPTv3  # noqa: F401
 from .keypoint_swin3d import KeypointSwin3D  # noqa: F401
 from .keypoint_swin3d_vote import KeypointSwin3DVote  # noqa: F401
 from .keypoint_ptv1 import KeypointPTv1  # noqa: F401
+from .oacnns import OACNNs  # noqa: F401
+from .keypoint_oa_cnns import KeypointOACNNs  # noqa: F401

@@ -359,6 +359,21 @@ class ClusterGatherFn(Function):
         return ops.segment_sum(dy.contiguous(), order0, seg_start, ctx.n_out), None, None, None
 
 
+class SegmentSumFn(Function):
+    """torch_geometric scatter(x, cluster, reduce="sum") of the OA-CNNs aggregator (oacnns_v1m1_base.py:92-97) over the
+    sorted-order runs of a partition: fixed-order forward (no atomics), gather backward."""
+
+    @staticmethod
+    def forward(ctx, x, cluster, order0, seg_start, n_out):
+        ctx.save_for_backward(cluster)
+        return ops.segment_sum(x.contiguous(), order0, seg_start, n_out)
+
+    @staticmethod
+    def backward(ctx, dy):
+        cluster, = ctx.saved_tensors
+        return dy.index_select(0, cluster), None, None, None, None
+
+
 class SceneMeanFn(Function):
     """(B, C) fp32 per-scene column mean of feat (N, C): torch_scatter.scatter_mean(feat, batch, dim=0)
     (keypoint_ptv3.py:44) / the per-scene mean loop of keypoint_swin3d.py:109-117.  Backward: dfeat[i] =
@@ -455,6 +470,10 @@ def segment_max(feat, order0, seg_start, n_out):
 
 def cluster_gather(feat, cluster, order0, seg_start):
     return ClusterGatherFn.apply(feat, cluster, order0, seg_start)
+
+
+def segment_sum(x, cluster, order0, seg_start, n_out):
+    return SegmentSumFn.apply(x, cluster, order0, seg_start, n_out)
 
 
 # -------------------------------------------------------------------------------------------------

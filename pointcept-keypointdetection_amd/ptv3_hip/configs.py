@@ -69,6 +69,13 @@ KEYPOINT_SWIN3D_VOTE_CFG = dict(OFFSET_SWIN3D_CFG, type="KeypointSwin3DVote", vo
                                 backbone_conf=dict(OFFSET_SWIN3D_CFG["backbone_conf"]))
 # the fork's Point Transformer V1 regression model (configs/my_dataset/keypoint_ptv1.py:20-28)
 KEYPOINT_PTV1_CFG = dict(type="KeypointPTv1-50", in_channels=7, num_keypoints=6, hidden_dim=256)
+# the fork's OA-CNNs regression model (configs/my_dataset/keypoint_oa_cnns.py:12-29), run at batch size 8
+KEYPOINT_OACNNS_CFG = dict(
+    type="KeypointOACNNs", num_keypoints=6, in_channels=4, embed_channels=64, enc_channels=[64, 64, 128, 256],
+    groups=[4, 4, 8, 16], enc_depth=[3, 3, 9, 8], dec_channels=[256, 256, 256, 256],
+    point_grid_size=[[8, 12, 16, 16], [6, 9, 12, 12], [4, 6, 8, 8], [3, 4, 6, 6]], dec_depth=[2, 2, 2, 2],
+    enc_num_ref=[16, 16, 16, 16], hidden_dim=256,
+)
 
 # plumbing-size Swin3D: three levels, both head widths the kernel is built for (8 and 16)
 TINY_SWIN3D_CFG = dict(

@@ -146,6 +146,15 @@ SIGNATURES = {
     "ptv3_interpolation_backward": (c_int, [c_int, c_int, c_int, P, P, P, P, P]),
     "ptv3_farthest_point_sampling": (c_int, [c_int, c_int, P, P, P, P, P, P]),
     "ptv3_vector_attn_fwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "ptv3_down2_keys": (c_int, [P, c_int64, c_int, c_int, c_int, c_int64, P, P, P]),
+    "ptv3_down2_children": (c_int, [P, P, P, P, P, P, P, c_int64, c_int64, P, P, P, P, P, P]),
+    "ptv3_down2_conv": (c_int, [P, P, P, c_int64, c_int64, c_int, c_int, P, P, c_int, P, P]),
+    "ptv3_up2_conv": (c_int, [P, P, P, P, P, c_int64, c_int64, c_int, c_int, P, P, c_int, P, P]),
+    "ptv3_cluster_keys": (c_int, [P, c_int64, P, c_int, P, P]),
+    "ptv3_cluster_center": (c_int, [P, c_int64, P, P, P, c_int64, c_int, P, P]),
+    "ptv3_cluster_softmax_sum": (c_int, [P, c_int64, P, c_int64, P, P, P, P, c_int64, c_int, P, P]),
+    "ptv3_cluster_mix": (c_int, [P, c_int64, P, P, c_int, P, c_int64, c_int64, c_int, P, c_int64, c_int, P]),
+    "ptv3_add_act": (c_int, [P, P, c_int, P, c_int64, P]),
 }
 
 

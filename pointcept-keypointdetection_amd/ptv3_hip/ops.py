@@ -1261,3 +1261,216 @@ def profile_collect():
     la = (ctypes.c_int64 * n)()
     lib.check(lib.ptv3_profile_collect(ms, fl, by, la), "ptv3_profile_collect")
     return {FAMILIES[i]: dict(ms=ms[i], flops=fl[i], bytes=by[i], launches=int(la[i])) for i in range(n)}
+
+
+# ---------------------------------------------------------------------------------------------
+# OA-CNNs: the kernel-2 / stride-2 sparse conv pair and the adaptive aggregator (fp32)
+# ---------------------------------------------------------------------------------------------
+def _chk_rows(t, name, cols=None):
+    """fp32 (m, C) GPU matrix whose rows may be a column slice of a wider matrix (unit column stride, 16-byte aligned)."""
+    if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+        raise TypeError(f"{name}: expected a 2-d float32 GPU tensor")
+    if t.stride(1) != 1 or t.stride(0) % 4 or t.storage_offset() % 4 or t.stride(0) < t.shape[1]:
+        raise RuntimeError(f"{name}: rows must be contiguous, 16-byte aligned and at a stride that is a multiple of 4")
+    if cols is not None and t.shape[1] != cols:
+        raise RuntimeError(f"{name}: {t.shape[1]} columns, expected {cols}")
+
+
+class Down2Plan:
+    """Index plan of one SparseConv3d(kernel_size=2, stride=2) and of the SparseInverseConv3d that shares its indice_key:
+    parent (n) int32 (-1: the parent lies outside the coarse shape), tap (n) int32, child (m_out, 8) int32, coarse
+    (m_out, 4) int32 sites ordered by (b, x, y, z), up_rows (n) int32 = rows sorted by tap, tap_start (10 host ints)."""
+
+    def __init__(self, n, m_out, parent, tap, child, coarse, up_rows, tap_start, out_shape):
+        self.n, self.m_out, self.parent, self.tap, self.child, self.coarse = n, m_out, parent, tap, child, coarse
+        self.up_rows, self.tap_start, self.out_shape = up_rows, tap_start, out_shape
+        self.tap_start_c = (ctypes.c_int32 * 10)(*tap_start)
+        self._long = None
+
+    @property
+    def dropped(self):
+        return self.tap_start[9] - self.tap_start[8]
+
+    def long_indices(self):
+        """(child with -1 -> n_in, parent with -1 -> m_out, up_rows, inverse of up_rows) as int64, for torch indexing."""
+        if self._long is None:
+            child = torch.where(self.child >= 0, self.child, self.n).long()
+            parent = torch.where(self.parent >= 0, self.parent, self.m_out).long()
+            rows = self.up_rows.long()
+            inv = torch.empty_like(rows)
+            inv[rows] = torch.arange(self.n, device=rows.device)
+            self._long = (child, parent, rows, inv)
+        return self._long
+
+
+def down2_plan(indices, spatial_shape, batch_size):
+    """Plan of the strided pair for unique sites `indices` (n, 4) int32 [b, x, y, z]; ONE host read (ten counters)."""
+    _chk(indices, "indices", torch.int32, 2)
+    n, dev = indices.shape[0], indices.device
+    out_shape = [(int(s) - 2) // 2 + 1 for s in spatial_shape]
+    if min(out_shape) < 1:
+        raise ValueError(f"down2_plan: spatial shape {list(spatial_shape)} is under 2 on some axis")
+    none_key = int(batch_size) * out_shape[0] * out_shape[1] * out_shape[2]
+    key = torch.empty(n, dtype=torch.int64, device=dev)
+    tap = torch.empty(n, dtype=torch.int32, device=dev)
+    lib.check(lib.ptv3_down2_keys(_p(indices), n, out_shape[0], out_shape[1], out_shape[2], none_key, _p(key), _p(tap),
+                                  _stream()), "ptv3_down2_keys")
+    order = argsort_codes(key.view(1, -1), max(1, none_key.bit_length()))[0][0]
+    rank = torch.empty(n, dtype=torch.int64, device=dev)
+    seg_start = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    n_out = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = lib.ptv3_pool_workspace_bytes(n)
+    ws = _ws(ws_bytes, dev)
+    lib.check(lib.ptv3_pool_segments(_p(key), _p(order), n, 0, None, _p(rank), _p(seg_start), _p(n_out), None, _p(ws),
+                                     ws_bytes, _stream()), "ptv3_pool_segments")
+    parent = torch.empty(n, dtype=torch.int32, device=dev)
+    child = torch.full((n, 8), -1, dtype=torch.int32, device=dev)
+    coarse = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    up_key = torch.empty(n, dtype=torch.int64, device=dev)
+    counts = torch.zeros(10, dtype=torch.int32, device=dev)
+    lib.check(lib.ptv3_down2_children(_p(indices), _p(key), _p(tap), _p(rank), _p(order), _p(seg_start), _p(n_out), n,
+                                      none_key, _p(parent), _p(child), _p(coarse), _p(up_key), _p(counts), _stream()),
+              "ptv3_down2_children")
+    up_rows = argsort_codes(up_key.view(1, -1), 4)[0][0].int()
+    host = counts.tolist()   # the level's one host read
+    tap_start = [0]
+    for c in host[1:]:
+        tap_start.append(tap_start[-1] + c)
+    m_out = host[0]
+    return Down2Plan(n, m_out, parent, tap, child[:m_out], coarse[:m_out], up_rows, tap_start, out_shape)
+
+
+def _epi(bn_scale, bn_shift, cout):
+    for t, nm in ((bn_scale, "bn_scale"), (bn_shift, "bn_shift")):
+        _chk(t, nm, torch.float32, 1)
+        if t is not None and t.numel() != cout:
+            raise RuntimeError("epilogue vector length != cout")
+
+
+def down2_conv(x, w, plan, bn_scale=None, bn_shift=None, act=ACT_NONE):
+    """SparseConv3d(kernel_size=2, stride=2): x (n, cin) fp32, w (cout, 2, 2, 2, cin) -> (m_out, cout)."""
+    _chk(x, "x", torch.float32, 2)
+    _chk(w, "w", torch.float32)
+    n, cin = x.shape
+    cout = w.shape[0]
+    if n != plan.n or w.numel() != cout * 8 * cin:
+        raise RuntimeError("down2_conv: shape mismatch")
+    _epi(bn_scale, bn_shift, cout)
+    out = torch.empty((plan.m_out, cout), dtype=torch.float32, device=x.device)
+    lib.check(lib.ptv3_down2_conv(_p(x), _p(w), _p(plan.child), n, plan.m_out, cin, cout, _p(bn_scale), _p(bn_shift),
+                                  int(act), _p(out), _stream()), "ptv3_down2_conv")
+    return out
+
+
+def up2_conv(y, w, plan, bn_scale=None, bn_shift=None, act=ACT_NONE):
+    """SparseInverseConv3d(kernel_size=2) on the plan of its down conv: y (m_out, cin), w (cout, 2, 2, 2, cin) ->
+    (n, cout) on the fine sites in their own order; a site without a parent gets the epilogue of zero."""
+    _chk(y, "y", torch.float32, 2)
+    _chk(w, "w", torch.float32)
+    m, cin = y.shape
+    cout = w.shape[0]
+    if m != plan.m_out or w.numel() != cout * 8 * cin:
+        raise RuntimeError("up2_conv: shape mismatch")
+    _epi(bn_scale, bn_shift, cout)
+    out = torch.empty((plan.n, cout), dtype=torch.float32, device=y.device)
+    lib.check(lib.ptv3_up2_conv(_p(y), _p(w), _p(plan.parent), _p(plan.up_rows), plan.tap_start_c, plan.n, m, cin, cout,
+                                _p(bn_scale), _p(bn_shift), int(act), _p(out), _stream()), "ptv3_up2_conv")
+    return out
+
+
+class ClusterPlan:
+    """One partition of a level's rows: order (m) int64, seg_start (m + 1) int32, cluster (m) int64 ids, and the cluster
+    count on the device (count_dev); count() reads it once, for the taped composition only."""
+
+    def __init__(self, m, order, seg_start, cluster, count_dev):
+        self.m, self.order, self.seg_start, self.cluster, self.count_dev = m, order, seg_start, cluster, count_dev
+        self._count = None
+
+    def count(self):
+        if self._count is None:
+            self._count = int(self.count_dev.item())
+        return self._count
+
+
+def cluster_plan(indices, min_xyz, g):
+    """voxel_grid(pos, size=g, batch) + torch.unique(return_inverse) of DonwBlock.forward, without a host read."""
+    _chk(indices, "indices", torch.int32, 2)
+    _chk(min_xyz, "min_xyz", torch.int32, 1)
+    m, dev = indices.shape[0], indices.device
+    key = torch.empty(m, dtype=torch.int64, device=dev)
+    lib.check(lib.ptv3_cluster_keys(_p(indices), m, _p(min_xyz), int(g), _p(key), _stream()), "ptv3_cluster_keys")
+    order = argsort_codes(key.view(1, -1), 63)[0][0]
+    cluster = torch.empty(m, dtype=torch.int64, device=dev)
+    seg_start = torch.empty(m + 1, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = lib.ptv3_pool_workspace_bytes(m)
+    ws = _ws(ws_bytes, dev)
+    lib.check(lib.ptv3_pool_segments(_p(key), _p(order), m, 0, None, _p(cluster), _p(seg_start), _p(count), None, _p(ws),
+                                     ws_bytes, _stream()), "ptv3_pool_segments")
+    return ClusterPlan(m, order, seg_start, cluster, count)
+
+
+def cluster_center(x, plan):
+    """x - clustermean(x)[cluster] (oacnns_v1m1_base.py:92); x may be a column slice."""
+    _chk_rows(x, "x")
+    m, c = x.shape
+    if m != plan.m:
+        raise RuntimeError("cluster_center: row count != plan")
+    out = torch.empty((m, c), dtype=torch.float32, device=x.device)
+    lib.check(lib.ptv3_cluster_center(_p(x), x.stride(0), _p(plan.order), _p(plan.seg_start), _p(plan.count_dev), m, c,
+                                      _p(out), _stream()), "ptv3_cluster_center")
+    return out
+
+
+def cluster_softmax_sum(p, v, global_max, plan):
+    """agg (m, C), first count rows valid: clustersum(v e) / (clustersum(e) + 1e-6), e = exp(p - global_max) (:94-97)."""
+    _chk_rows(p, "p")
+    _chk_rows(v, "v", p.shape[1])
+    _chk(global_max, "global_max", torch.float32)
+    m, c = p.shape
+    if m != plan.m or v.shape[0] != m or global_max.numel() != 1:
+        raise RuntimeError("cluster_softmax_sum: shape mismatch")
+    agg = torch.empty((m, c), dtype=torch.float32, device=p.device)
+    lib.check(lib.ptv3_cluster_softmax_sum(_p(p), p.stride(0), _p(v), v.stride(0), _p(global_max), _p(plan.order),
+                                           _p(plan.seg_start), _p(plan.count_dev), m, c, _p(agg), _stream()),
+              "ptv3_cluster_softmax_sum")
+    return agg
+
+
+def cluster_mix(logits, aggs, plans, head=None):
+    """mixed[i] = sum_l softmax(logits[i, :L])[l] * aggs[l][plans[l].cluster[i]] (:99-102).  With `head` (m, C) returns
+    cat([head, mixed], 1) in one buffer, the input of `fuse` (:103-104)."""
+    if not logits.is_cuda or logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise TypeError("logits: expected a 2-d float32 GPU tensor with contiguous rows")   # read value by value
+    levels = len(aggs)
+    if logits.shape[1] != levels:
+        raise RuntimeError("cluster_mix: one logit column per aggregate")
+    if len(plans) != levels:
+        raise RuntimeError("cluster_mix: one plan per aggregate")
+    m = logits.shape[0]
+    c = aggs[0].shape[1] if levels else 0
+    for a in aggs:
+        _chk(a, "agg", torch.float32, 2)
+        if a.shape[1] != c or a.shape[0] < m:
+            raise RuntimeError("cluster_mix: aggregates must be (m, C)")
+    if head is not None:
+        _chk_rows(head, "head", c)
+    ap = (ctypes.c_void_p * max(levels, 1))(*[a.data_ptr() for a in aggs])
+    cp = (ctypes.c_void_p * max(levels, 1))(*[q.cluster.data_ptr() for q in plans])
+    ocol = c if head is not None else 0
+    out = torch.empty((m, ocol + c), dtype=torch.float32, device=logits.device)
+    lib.check(lib.ptv3_cluster_mix(_p(logits), logits.stride(0), ap, cp, levels, _p(head),
+                                   head.stride(0) if head is not None else 0, m, c, _p(out), ocol + c, ocol, _stream()),
+              "ptv3_cluster_mix")
+    return out
+
+
+def add_act(a, b, act=ACT_NONE):
+    """act(a + b) for two fp32 tensors of one shape."""
+    _chk(a, "a", torch.float32)
+    _chk(b, "b", torch.float32)
+    if a.shape != b.shape:
+        raise RuntimeError("add_act: shape mismatch")
+    out = torch.empty_like(a)
+    lib.check(lib.ptv3_add_act(_p(a), _p(b), int(act), _p(out), a.numel(), _stream()), "ptv3_add_act")
+    return out
