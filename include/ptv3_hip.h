@@ -339,7 +339,8 @@ int ptv3_forward(const ptv3_model_desc* desc, const void* const* params, int num
  *   (:277-284, 499-506) in the layout of ptv3_gemm's w.  Input gradients reuse ptv3_gemm itself: linear with
  *   w^T; sparse conv with w'[c][t][o] = w[o][kvol-1-t][c] (submanifold neighbour maps are symmetric).
  * dbias (cout) fp32 or NULL: the bias gradient sum_i dy[i][:] from the same pass (the staging of dy sees every
- *   element once; a separate column reduction would read dy again and cost two more launches per layer). */
+ *   element once; a separate column reduction would read dy again and cost two more launches per layer).
+ * m == 0: dw and dbias are zeroed; dy, x and nbr are not read and may be NULL. */
 size_t ptv3_gemm_tn_workspace_bytes(int64_t m, int cout, int cin, int kvol);
 int ptv3_gemm_tn(const void* dy, const void* x, const int32_t* nbr, float* dw, float* dbias, int64_t m, int cout,
                  int cin, int kvol, int dtype, void* workspace, size_t workspace_bytes, void* stream);

@@ -729,7 +729,8 @@ extern "C" int ptv3_gemm_tn(const void* dy, const void* x, const int32_t* nbr, f
   BWD_DTYPE_CHECK("gemm_tn");
   PTV3_REQUIRE(cout > 0 && cin > 0 && kvol >= 1 && m >= 0, "gemm_tn: bad shape m=%lld cout=%d cin=%d kvol=%d",
                (long long)m, cout, cin, kvol);
-  PTV3_REQUIRE((kvol == 1) == (nbr == nullptr), "gemm_tn: nbr must be given exactly when kvol > 1");
+  // (an empty table has no storage: with m == 0 a convolution's nbr may be NULL)
+  PTV3_REQUIRE(m == 0 || (kvol == 1) == (nbr == nullptr), "gemm_tn: nbr must be given exactly when kvol > 1");
   hipStream_t s = (hipStream_t)stream;
   const int64_t nw = (int64_t)cout * kvol * cin;
   if (m == 0) {
