@@ -765,6 +765,46 @@ int ptv3_cluster_mix(const float* logits, int64_t ldl, const float* const* agg_h
 /* out = act(a + b) over `count` fp32 values (count % 4 == 0): the block's closing relu(x + res) (:109) */
 int ptv3_add_act(const float* a, const float* b, int act, float* out, int64_t count, void* stream);
 
+/* ---- Point Transformer V2 grouped vector attention, eval forward -------------------------------------
+ * GroupedVectorAttention.forward after its three input projections (pointcept/models/point_transformer_v2/
+ * point_transformer_v2m2_base.py:116-136, pe_bias = True, pe_multiplier = False) in one launch: both pointops.grouping
+ * calls, linear_p_bias, weight_encoding, the softmax, the mask and the einsum.  q / k / v (n,c) fp32, xyz (n,3) fp32,
+ * idx (n,ns) int32 (-1, or anything outside [0,n), = missing), out (n,c) fp32.  With j = idx[i,s], I = c / groups and every
+ * PointBatchNorm folded to a per-channel (scale s, shift t) that also carries the bias of the Linear in front of it:
+ *   pos = xyz[j] - xyz[i]                                  (0 where j is missing)
+ *   h   = relu(s_p * (w_p1 pos) + t_p)                     w_p1 (c,3), s_p / t_p (c)
+ *   peb = w_p2 h + b_p2                                    w_p2 (c,c), b_p2 (c)     v_mfma_f32_16x16x4_f32, w_p2 streamed
+ *   r   = k[j] - q[i] + peb                                (k[j] = 0 where j is missing)
+ *   w   = w_w2 relu(s_w * (w_w1 r) + t_w) + b_w2           w_w1 (groups,c), s_w / t_w (groups), w_w2 (groups,groups)
+ *   w   = softmax over the ns slots, per group; then w = 0 where j is missing (:129-132: after the softmax, no
+ *         renormalisation; the missing slot took part with pos = 0, k = v = 0, peb = MLP(0))
+ *   out[i, g*I + t] = sum_s (v[j, g*I + t] + peb[s, g*I + t]) * w[s, g]
+ * h, peb, r and w live in registers and LDS only.  c: a multiple of 8 in [8,512]; groups: a divisor of c, at most 64;
+ * ns in [1,32]; 0 <= n < 2^31 (n = 0 returns PTV3_OK without a launch); anything else, a NULL pointer included, is
+ * refused with PTV3_ERR_ARG before any launch.  fp32 arithmetic, fixed summation order, no atomics: bitwise
+ * reproducible. */
+int ptv3_gva_fwd(const float* q, const float* k, const float* v, const float* xyz, const int32_t* idx, int64_t n, int c,
+                 int groups, int ns, const float* w_p1, const float* s_p, const float* t_p, const float* w_p2,
+                 const float* b_p2, const float* w_w1, const float* s_w, const float* t_w, const float* w_w2,
+                 const float* b_w2, float* out, void* stream);
+
+/* ---- Point Transformer V2 grid pooling (GridPool.forward, :251-276; PARITY UNPINNED) --------------------
+ * The reference computes the partition with torch_scatter.segment_csr and torch_geometric's voxel_grid (torch_cluster
+ * grid_cluster), none of which is in its tree; their published semantics are restated here.
+ * ptv3_grid_keys: start[b] (num_scenes,3) = per-axis minimum of scene b's coordinates (:255-263), cell = (int64)((coord -
+ * start[b]) / size) per axis in fp32 (a subtraction, then a correctly rounded division: the two operations torch
+ * performs), key[i] = b << 51 | cz << 34 | cy << 17 | cx: ascending keys are the rank order torch.unique gives
+ * voxel_grid's ids (x fastest, batch slowest), so ptv3_argsort_i64(key, end_bit 63) + ptv3_pool_segments(key, order,
+ * shift 0, batch) yield `cluster`, the sorted order, the segments and the pooled offsets.  offset: (num_scenes) int64
+ * cumulative scene ends on the device; batch (n) int64 out; *bad (device, zeroed by the caller) is set to 1 when a
+ * cell does not fit 17 bits.  1 <= num_scenes <= 4096.
+ * ptv3_segment_mean3: out[j] = mean of coord over the members order[seg_start[j] .. seg_start[j+1]) (:272), summed in
+ * that order.  The feature max (:273) is ptv3_pool_reduce's feature half. */
+int ptv3_grid_keys(const float* coord, int64_t n, const int64_t* offset, int num_scenes, float size, float* start,
+                   int64_t* key, int64_t* batch, int64_t* bad, void* stream);
+int ptv3_segment_mean3(const float* coord, const int64_t* order, const int32_t* seg_start, int64_t n_out, float* out,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,3 +16,5 @@ from .keypoint_swin3d_vote import KeypointSwin3DVote  # noqa: F401
 from .keypoint_ptv1 import KeypointPTv1  # noqa: F401
 from .oacnns import OACNNs  # noqa: F401
 from .keypoint_oa_cnns import KeypointOACNNs  # noqa: F401
+from .point_transformer_v2 import PointTransformerV2  # noqa: F401
+from .keypoint_ptv2 import KeypointPTv2  # noqa: F401

@@ -3,8 +3,8 @@
 Same Python surface as libs/pointops/functions/__init__.py:1-14 for the three op families on the hot
 path and for farthest point sampling (KeypointPTv1's TransitionDown); `import pointops`
 is a hard import of the reference's trainer hooks (engines/hooks/evaluator.py:12).  The other families (ball query,
-subtraction, aggregation, attention steps) serve PTv2 / Stratified-Transformer / the unfused PTv1 variants only and
-raise NotImplementedError.
+subtraction, aggregation, attention steps) serve the unfused PTv2 modes / Stratified-Transformer / the unfused PTv1
+variants only and raise NotImplementedError (PT-v2m2's attention is the fused ptv3_gva_fwd over knn_query and grouping).
 """
 from .functions import (knn_query, grouping, grouping2, interpolation, interpolation2, knn_query_and_group,
                         offset2batch, batch2offset, farthest_point_sampling)  # noqa: F401

@@ -77,6 +77,18 @@ KEYPOINT_OACNNS_CFG = dict(
     enc_num_ref=[16, 16, 16, 16], hidden_dim=256,
 )
 
+# the fork's Point Transformer V2 regression model (configs/my_dataset/keypoint_ptv2.py:11-54), run at batch size 8
+KEYPOINT_PTV2_CFG = dict(
+    type="KeypointPTv2", num_keypoints=6, hidden_dim=256,
+    backbone_conf=dict(
+        type="PT-v2m2", in_channels=4, num_classes=0, patch_embed_depth=1, patch_embed_channels=48,
+        patch_embed_groups=6, patch_embed_neighbours=8, enc_depths=(2, 2, 6, 2), enc_channels=(96, 192, 384, 512),
+        enc_groups=(12, 24, 48, 64), enc_neighbours=(16, 16, 16, 16), dec_depths=(1, 1, 1, 1),
+        dec_channels=(48, 96, 192, 384), dec_groups=(6, 12, 24, 48), dec_neighbours=(16, 16, 16, 16),
+        grid_sizes=(0.06, 0.12, 0.24, 0.48), attn_qkv_bias=True, pe_multiplier=False, pe_bias=True, attn_drop_rate=0.0,
+        drop_path_rate=0.3, enable_checkpoint=False, unpool_backend="map"),
+)
+
 # plumbing-size Swin3D: three levels, both head widths the kernel is built for (8 and 16)
 TINY_SWIN3D_CFG = dict(
     type="Swin3D-v1m1", in_channels=9, num_classes=13, base_grid_size=0.02, depths=[2, 2, 2], channels=[16, 32, 32],

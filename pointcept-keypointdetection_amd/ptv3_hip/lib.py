@@ -155,6 +155,9 @@ SIGNATURES = {
     "ptv3_cluster_softmax_sum": (c_int, [P, c_int64, P, c_int64, P, P, P, P, c_int64, c_int, P, P]),
     "ptv3_cluster_mix": (c_int, [P, c_int64, P, P, c_int, P, c_int64, c_int64, c_int, P, c_int64, c_int, P]),
     "ptv3_add_act": (c_int, [P, P, c_int, P, c_int64, P]),
+    "ptv3_gva_fwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "ptv3_grid_keys": (c_int, [P, c_int64, P, c_int, c_float, P, P, P, P, P]),
+    "ptv3_segment_mean3": (c_int, [P, P, P, c_int64, P, P]),
 }
 
 

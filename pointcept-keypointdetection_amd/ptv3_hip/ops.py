@@ -1474,3 +1474,87 @@ def add_act(a, b, act=ACT_NONE):
     out = torch.empty_like(a)
     lib.check(lib.ptv3_add_act(_p(a), _p(b), int(act), _p(out), a.numel(), _stream()), "ptv3_add_act")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Point Transformer V2: grouped vector attention, grid pooling
+# ---------------------------------------------------------------------------------------------
+def grouped_vector_attention(q, k, v, xyz, idx, groups, w_p1, s_p, t_p, w_p2, b_p2, w_w1, s_w, t_w, w_w2, b_w2):
+    """out (n, c) fp32: GroupedVectorAttention.forward after the input projections (pe_bias only) over the neighbour rows
+    idx (n, ns) int32 (-1 = missing), PointBatchNorms folded (fold_batchnorm); formulas and weight shapes: ptv3_gva_fwd
+    in include/ptv3_hip.h."""
+    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (xyz, "xyz")):
+        _chk(t, nm, torch.float32, 2)
+    _chk(idx, "idx", torch.int32, 2)
+    n, c = q.shape
+    ns, g = idx.shape[1], int(groups)
+    if k.shape != q.shape or v.shape != q.shape or tuple(xyz.shape) != (n, 3) or idx.shape[0] != n:
+        raise RuntimeError("grouped_vector_attention: q / k / v (n, c), xyz (n, 3) and idx (n, ns) disagree")
+    shapes = ((w_p1, (c, 3)), (s_p, (c,)), (t_p, (c,)), (w_p2, (c, c)), (b_p2, (c,)), (w_w1, (g, c)), (s_w, (g,)),
+              (t_w, (g,)), (w_w2, (g, g)), (b_w2, (g,)))
+    for i, (t, shape) in enumerate(shapes):
+        _chk(t, f"grouped_vector_attention weight {i}", torch.float32)
+        if g >= 1 and c % g == 0 and tuple(t.shape) != shape:
+            raise RuntimeError(f"grouped_vector_attention: weight {i} has shape {tuple(t.shape)}, expected {shape}")
+    out = torch.empty_like(q)
+    lib.check(lib.ptv3_gva_fwd(_p(q), _p(k), _p(v), _p(xyz), _p(idx), n, c, g, ns, *[_p(t) for t, _ in shapes],
+                               _p(out), _stream()), "ptv3_gva_fwd")
+    return out
+
+
+class GridPoolPlan:
+    """The partition of one GridPool: cluster (n) int64 = pooled row of every point, order (n) int64 = points sorted by
+    cell, seg_start (n_out + 1) int32 = the clusters' runs in `order`, n_out, the pooled cumulative scene ends on the
+    device (int64) and on the host, and start (b, 3) = every scene's minimum corner."""
+
+    def __init__(self, cluster, order, seg_start, n_out, offset, offset_host, start):
+        self.cluster, self.order, self.seg_start, self.n_out = cluster, order, seg_start, n_out
+        self.offset, self.offset_host, self.start = offset, offset_host, start
+
+
+def grid_pool_plan(coord, offset, size):
+    """GridPool.forward's partition (point_transformer_v2m2_base.py:253-275) of coord (n, 3) fp32 with cumulative scene
+    ends offset (b) on the device, n >= 1: segment min, voxel_grid, torch.unique(sorted, return_inverse) and torch.sort
+    as ptv3_grid_keys + ptv3_argsort_i64 + ptv3_pool_segments.  One host read: the pooled offsets (their last entry is
+    the pooled row count) together with the flag of a cell outside the key's 17 bits per axis."""
+    _chk(coord, "coord", torch.float32, 2)
+    off = _scene_offset(offset, "offset")
+    n, b, dev = coord.shape[0], off.shape[0], coord.device
+    if coord.shape[1] != 3 or n < 1:
+        raise RuntimeError("grid_pool_plan: coord must be (n, 3) with n >= 1")
+    start = torch.empty((b, 3), dtype=torch.float32, device=dev)
+    key = torch.empty(n, dtype=torch.int64, device=dev)
+    batch = torch.empty(n, dtype=torch.int64, device=dev)
+    # pooled offsets (b), a scene without points keeps -1; the last slot is the out-of-range flag
+    tail = torch.full((b + 1,), -1, dtype=torch.int64, device=dev)
+    tail[b] = 0
+    lib.check(lib.ptv3_grid_keys(_p(coord), n, _p(off), b, float(size), _p(start), _p(key), _p(batch),
+                                 tail.data_ptr() + 8 * b, _stream()), "ptv3_grid_keys")
+    order = argsort_codes(key.view(1, -1), 63)[0][0]
+    cluster = torch.empty(n, dtype=torch.int64, device=dev)
+    seg_start = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    n_out = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = lib.ptv3_pool_workspace_bytes(n)
+    ws = _ws(ws_bytes, dev)
+    lib.check(lib.ptv3_pool_segments(_p(key), _p(order), n, 0, _p(batch), _p(cluster), _p(seg_start), _p(n_out),
+                                     _p(tail), _p(ws), ws_bytes, _stream()), "ptv3_pool_segments")
+    host = [int(v) for v in tail.tolist()]      # the one read
+    if host[b]:
+        raise ValueError(f"grid_pool_plan: a scene spans more than {1 << 17} cells of size {size} along an axis")
+    host = host[:b]
+    if min(host) < 0:
+        raise ValueError("grid_pool_plan: a scene without points")
+    return GridPoolPlan(cluster, order, seg_start[:host[-1] + 1], host[-1], tail[:b], host, start)
+
+
+def segment_mean3(coord, order, seg_start, n_out):
+    """(n_out, 3) fp32: mean of coord (n, 3) over every run of `order` (segment_csr(coord[order], ptr, "mean"))."""
+    _chk(coord, "coord", torch.float32, 2)
+    _chk(order, "order", torch.int64, 1)
+    _chk(seg_start, "seg_start", torch.int32, 1)
+    if coord.shape[1] != 3 or seg_start.shape[0] != n_out + 1:
+        raise RuntimeError("segment_mean3: coord (n, 3) and seg_start (n_out + 1) expected")
+    out = torch.empty((n_out, 3), dtype=torch.float32, device=coord.device)
+    lib.check(lib.ptv3_segment_mean3(_p(coord), _p(order), _p(seg_start), n_out, _p(out), _stream()),
+              "ptv3_segment_mean3")
+    return out
