@@ -200,6 +200,26 @@ int ptv3_block_tail(const void* attn, const void* f1, const void* wproj, const f
                     const float* b2, const void* w1, const float* bias1, const void* w2, const float* bias2,
                     void* out, int64_t m, int c, int hidden, float eps, int dtype, void* stream);
 
+/* ---- bottleneck xCPE of PT-v3m1-Plus (pointcept/models/keypoint_ptv3_plus.py:68-94; csrc/cpe_plus.hip) ----------
+ * ptv3_rows_linear_ln: cpe[0..2] = SubMConv3d(C, mid, 1, bias=False) -> LayerNorm(mid) -> ReLU (:70-72) in one launch:
+ *   out = act(LayerNorm(x @ w^T [+ bias]; gamma, beta, eps)),  x (m, c), w (cout, c), out (m, cout)
+ *   c in {16, 32, 64, 128, 256, 512}, cout in {16, 32, 64, 128}.
+ * ptv3_subm_conv_ln: cpe[3..5] = SubMConv3d(mid, mid, k, bias=True) -> LayerNorm(mid) -> ReLU (:76-85) in one launch:
+ *   out = act(LayerNorm(sum_t w[:, t, :] x[nbr[i][t]] [+ bias]; gamma, beta, eps)),  x / out (m, c), w (c, kvol, c) as
+ *   ptv3_gemm takes it, nbr (m, kvol) as ptv3_subm_neighbors writes it, row_order as in ptv3_gemm (locality only);
+ *   c in {16, 32, 64, 128}, kvol in {27, 125}.
+ * x / w / out in `dtype`, bias / gamma / beta fp32; products accumulate in fp32 and the LayerNorm statistics are taken
+ * in fp32 on the unrounded sums, inside one wave in a fixed order (bitwise reproducible).  A table entry outside
+ * [0, m) counts as an absent tap.  Any other shape: PTV3_ERR_UNSUPPORTED with ptv3_last_error set, before any launch;
+ * the *_capable queries answer the same question without an error. */
+int ptv3_rows_linear_ln_capable(int c, int cout, int dtype);
+int ptv3_rows_linear_ln(const void* x, const void* w, const float* bias, const float* gamma, const float* beta,
+                        void* out, int64_t m, int c, int cout, float eps, int act, int dtype, void* stream);
+int ptv3_subm_conv_ln_capable(int c, int kvol, int dtype);
+int ptv3_subm_conv_ln(const void* x, const void* w, const int32_t* nbr, const int32_t* row_order, const float* bias,
+                      const float* gamma, const float* beta, void* out, int64_t m, int c, int kvol, float eps, int act,
+                      int dtype, void* stream);
+
 /* ---- normalisation / elementwise -------------------------------------------------------------
  * torch.nn.LayerNorm over the last dim (Block.cpe[2], norm1, norm2; :277-304): y = LN(x)*g+b [+ res];
  * optional second output y2 = LN2(y) * g2 + b2 (fuses `shortcut + cpe` with the following norm1). */

@@ -18,3 +18,4 @@ from .oacnns import OACNNs  # noqa: F401
 from .keypoint_oa_cnns import KeypointOACNNs  # noqa: F401
 from .point_transformer_v2 import PointTransformerV2  # noqa: F401
 from .keypoint_ptv2 import KeypointPTv2  # noqa: F401
+from .keypoint_ptv3_plus import BlockPlus, PointTransformerV3Plus, KeypointPTv3Plus  # noqa: F401

@@ -62,6 +62,11 @@ KEYPOINT_PTV3_CFG = dict(
                        pdnorm_adaptive=False, pdnorm_affine=True,
                        pdnorm_conditions=("ScanNet", "S3DIS", "Structured3D")),
 )
+# the fork's own backbone (configs/my_dataset/keypoint_ptv3_plus.py:11-56): PT-v3m1 widths, bottleneck 5^3 xCPE
+KEYPOINT_PTV3_PLUS_CFG = dict(
+    type="KeypointPTv3Plus", num_keypoints=6, hidden_dim=256,
+    backbone_conf=dict(KEYPOINT_PTV3_CFG["backbone_conf"], type="PT-v3m1-Plus", cpe_kernel_size=5),
+)
 KEYPOINT_SWIN3D_CFG = dict(OFFSET_SWIN3D_CFG, type="KeypointSwin3D",
                            backbone_conf=dict(OFFSET_SWIN3D_CFG["backbone_conf"]))
 # the fork's voting model (configs/my_dataset/keypoint_swin3d_plus.py:14-52)

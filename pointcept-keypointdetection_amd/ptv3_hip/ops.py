@@ -420,6 +420,66 @@ def rows_linear(x, w, bias, act=ACT_NONE, res=None, ln=None, ln0=None, shortcut=
     return (f1, out) if ln0 is not None else out
 
 
+def rows_linear_ln_capable(c, cout, dtype):
+    return dtype in _DT and bool(lib.ptv3_rows_linear_ln_capable(int(c), int(cout), _DT[dtype]))
+
+
+def subm_conv_ln_capable(c, kvol, dtype):
+    return dtype in _DT and bool(lib.ptv3_subm_conv_ln_capable(int(c), int(kvol), _DT[dtype]))
+
+
+def _chk_ln(name, cout, bias, gamma, beta):
+    for t, nm in ((bias, "bias"), (gamma, "gamma"), (beta, "beta")):
+        _chk(t, f"{name}: {nm}", torch.float32, 1)
+        if t is not None and t.numel() != cout:
+            raise RuntimeError(f"{name}: {nm} has {t.numel()} entries, expected {cout}")
+
+
+def rows_linear_ln(x, w, bias, gamma, beta, eps=1e-5, act=ACT_RELU, out=None):
+    """act(LayerNorm(x @ w^T [+ bias]; gamma, beta)) in one launch (see ptv3_rows_linear_ln): x (m, c), w (cout, c)."""
+    _chk(x, "x", (torch.float32, torch.bfloat16), 2)
+    _chk(w, "w", x.dtype, 2)
+    m, c = x.shape
+    cout = w.shape[0]
+    if w.shape[1] != c:
+        raise RuntimeError(f"rows_linear_ln: weight {tuple(w.shape)} does not match x {tuple(x.shape)}")
+    _chk_ln("rows_linear_ln", cout, bias, gamma, beta)
+    if out is None:
+        out = torch.empty((m, cout), dtype=x.dtype, device=x.device)
+    _chk(out, "out", x.dtype, 2)
+    if tuple(out.shape) != (m, cout):
+        raise RuntimeError("rows_linear_ln: out shape mismatch")
+    lib.check(lib.ptv3_rows_linear_ln(_p(x), _p(w), _p(bias), _p(gamma), _p(beta), _p(out), m, c, cout, float(eps),
+                                      int(act), _dt(x), _stream()), "ptv3_rows_linear_ln")
+    return out
+
+
+def subm_conv_ln(x, w, nbr, bias, gamma, beta, eps=1e-5, act=ACT_RELU, row_order=None, out=None):
+    """act(LayerNorm(sum_t w[:, t, :] x[nbr[i][t]] [+ bias]; gamma, beta)) in one launch (see ptv3_subm_conv_ln):
+    x (m, c), w (c, kvol, c) or (c, kvol * c), nbr (m, kvol) int32 with -1 for absent taps."""
+    _chk(x, "x", (torch.float32, torch.bfloat16), 2)
+    _chk(w, "w", x.dtype)
+    _chk(nbr, "nbr", torch.int32, 2)
+    _chk(row_order, "row_order", torch.int32, 1)
+    m, c = x.shape
+    kvol = nbr.shape[1]
+    if nbr.shape[0] != m:
+        raise RuntimeError("subm_conv_ln: neighbour table has another row count than x")
+    if w.numel() != c * kvol * c:
+        raise RuntimeError(f"subm_conv_ln: weight has {w.numel()} elements, expected {c}x{kvol}x{c}")
+    if row_order is not None and row_order.shape[0] != m:
+        raise RuntimeError("subm_conv_ln: row_order length != m")
+    _chk_ln("subm_conv_ln", c, bias, gamma, beta)
+    if out is None:
+        out = torch.empty((m, c), dtype=x.dtype, device=x.device)
+    _chk(out, "out", x.dtype, 2)
+    if tuple(out.shape) != (m, c):
+        raise RuntimeError("subm_conv_ln: out shape mismatch")
+    lib.check(lib.ptv3_subm_conv_ln(_p(x), _p(w), _p(nbr), _p(row_order), _p(bias), _p(gamma), _p(beta), _p(out), m, c,
+                                    int(kvol), float(eps), int(act), _dt(x), _stream()), "ptv3_subm_conv_ln")
+    return out
+
+
 def block_head(x, slab, splits, conv_bias, shortcut, g0, b0, g1, b1, wqkv, bqkv, eps):
     """f1, qkv of the fused head (see ptv3_block_head)."""
     _chk(shortcut, "shortcut", (torch.float32, torch.bfloat16), 2)
