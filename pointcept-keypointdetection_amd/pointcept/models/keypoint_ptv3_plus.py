@@ -8,8 +8,10 @@ and so the same state_dict.  Against PT-v3m1 the backbone changes three things:
   * BlockPlus.cpe is a bottleneck (:68-94): 1x1 conv C -> mid, LayerNorm, ReLU, k^3 conv mid -> mid (k = 5 in the fork
     config), LayerNorm, ReLU, 1x1 conv mid -> C, Linear, LayerNorm; mid = C // 4, or C when that is below 16.
     Eval, fused: ptv3_rows_linear_ln, the k^3 conv (ptv3_subm_conv_ln where use_fused_cpe says it wins, else ptv3_gemm
-    + ptv3_layernorm + ReLU), one GEMM with the folded expand matrix W_lin W_up, then the row-local kernels Block uses.  set_fused(False), training, and kernel sizes the fused kernel does not serve run the
-    reference's statement order on the unfused layer ops.
+    + ptv3_layernorm + ReLU), one GEMM with the folded expand matrix W_lin W_up, then Block's own dispatch from the
+    CPE's last LayerNorm on (Block._eval_after_cpe; BlockPlus is a subclass of Block).  set_fused(False) and training
+    run the reference's statement order on the unfused layer ops; a kernel size the fused conv kernel does not serve
+    takes the composed conv.
   * every block attends along order 0 (:283, :334);
   * the encoder re-serializes after pooling at the stages with s % 3 != 0 (:389-454): the coordinate columns are
     permuted, one "z" order is computed, and the level is physically sorted by it.  All of it runs on the device.
@@ -28,11 +30,12 @@ from ptv3_hip import ops
 from ptv3_hip import autograd as A
 from pointcept.models.builder import MODELS
 from pointcept.models.utils.structure import Point
-from pointcept.models.utils.sparse import SubMConv3d, SparseConvTensor, _ParamCache
-from pointcept.models.utils.hip_layers import Linear, LayerNorm, BatchNorm1d, GELU, ReLU, DropPath, check_sync_batchnorm
+from pointcept.models.utils.sparse import SubMConv3d, SparseConvTensor
+from pointcept.models.utils.hip_layers import Linear, LayerNorm, BatchNorm1d, GELU, ReLU, check_sync_batchnorm
 from pointcept.models.modules import PointModule, PointSequential
 from pointcept.models.point_transformer_v3.point_transformer_v3m1_base import (
-    SerializedAttention, MLP, SerializedPooling, SerializedUnpooling, Embedding, PointTransformerV3, RPE, _add)  # noqa: F401
+    Block, SerializedAttention, MLP, SerializedPooling, SerializedUnpooling, Embedding, PointTransformerV3, RPE, _add,
+    _input_feat)  # noqa: F401
 from pointcept.models.keypoint_ptv3 import KeypointPTv3
 
 
@@ -80,39 +83,30 @@ class PointwiseConv3d(SubMConv3d):
         return x.replace_feature(ops.gemm(x.features, w, bias=bias, **epilogue))
 
 
-class BlockPlus(PointModule):
-    def __init__(self, channels, num_heads, patch_size=48, mlp_ratio=4.0, qkv_bias=True, qk_scale=None,
-                 attn_drop=0.0, proj_drop=0.0, drop_path=0.0, norm_layer=LayerNorm, act_layer=GELU,
-                 pre_norm=True, order_index=0, cpe_indice_key=None, enable_rpe=False, enable_flash=True,
-                 upcast_attention=True, upcast_softmax=True, cpe_kernel_size=3):
-        super().__init__()
-        self.channels = channels
-        self.pre_norm = pre_norm
+class BlockPlus(Block):
+    """Block with the bottleneck CPE (:27-153).  Training and set_fused(False) run Block's generic statement order (the
+    reference's :125-153) through the nine CPE modules; the native executor does not know this class."""
+
+    def __init__(self, *args, cpe_kernel_size=3, **kwargs):   # Block's signature, then cpe_kernel_size (:28-48)
+        super().__init__(*args, cpe_kernel_size=cpe_kernel_size, **kwargs)
         self.cpe_kernel_size = cpe_kernel_size
         self.fused = True
+
+    @staticmethod
+    def _build_cpe(channels, norm_layer, indice_key, cpe_kernel_size):
         mid = cpe_mid_channels(channels)
-        self.cpe = PointSequential(
+        return PointSequential(
             PointwiseConv3d(channels, mid, kernel_size=1, bias=False),
             norm_layer(mid),
             ReLU(inplace=True),
             SubMConv3d(mid, mid, kernel_size=cpe_kernel_size, padding=cpe_kernel_size // 2, bias=True,
-                       indice_key=cpe_indice_key),
+                       indice_key=indice_key),
             norm_layer(mid),
             ReLU(inplace=True),
             PointwiseConv3d(mid, channels, kernel_size=1, bias=False),
             Linear(channels, channels),
             norm_layer(channels),
         )
-        self.norm1 = PointSequential(norm_layer(channels))
-        self.attn = SerializedAttention(
-            channels=channels, patch_size=patch_size, num_heads=num_heads, qkv_bias=qkv_bias,
-            qk_scale=qk_scale, attn_drop=attn_drop, proj_drop=proj_drop, order_index=order_index,
-            enable_rpe=enable_rpe, enable_flash=enable_flash, upcast_attention=upcast_attention,
-            upcast_softmax=upcast_softmax)
-        self.norm2 = PointSequential(norm_layer(channels))
-        self.mlp = PointSequential(MLP(in_channels=channels, hidden_channels=int(channels * mlp_ratio),
-                                       out_channels=channels, act_layer=act_layer, drop=proj_drop))
-        self.drop_path = PointSequential(DropPath(drop_path) if drop_path > 0.0 else nn.Identity())
 
     def _fusable(self):
         c = self.cpe
@@ -123,31 +117,9 @@ class BlockPlus(PointModule):
     def expand_weight(self, dtype):
         """folded cpe[6] + cpe[7] in `dtype` (product taken in fp32), once per parameter version"""
         up, lin = self.cpe[6], self.cpe[7]
-        cache = self.__dict__.setdefault("_fold_cache", _ParamCache())
-        return cache.get(("expand", dtype), [up.weight, lin.weight],
-                         lambda: fold_expand(up.weight.detach().float(), lin.weight.detach().float()).to(dtype).contiguous())
-
-    def chain_weights(self, dtype):
-        """Block.chain_weights: (qkv, proj, fc1, fc2) in `dtype`, input channels permuted for the register-chained kernels"""
-        mlp = self.mlp[0]
-        cache = self.__dict__.setdefault("_fold_cache", _ParamCache())
-
-        def make():
-            cast = lambda w: w.detach().to(dtype).contiguous()  # noqa: E731
-            perm = ((lambda w: ops.chain_permute(w, dtype))
-                    if ops.block_fusable(self.channels, mlp.fc1.out_features, dtype) == 1 else (lambda w: w))
-            return (perm(cast(self.attn.qkv.weight)), cast(self.attn.proj.weight),
-                    perm(cast(mlp.fc1.weight)), perm(cast(mlp.fc2.weight)))
-        return cache.get(("chain", dtype), [self.attn.qkv.weight, self.attn.proj.weight, mlp.fc1.weight,
-                                            mlp.fc2.weight], make)
-
-    def _rows_path(self, feat):
-        """Block._rows_path with this block's last CPE LayerNorm"""
-        mlp = self.mlp[0]
-        n, c = feat.shape
-        return (n >= ops.rows_linear_rows() and isinstance(mlp.act, nn.GELU) and self.attn.qkv.bias is not None
-                and self.cpe[8].eps == self.norm1[0].eps == self.norm2[0].eps
-                and all(ops.rows_linear_capable(c, co, feat.dtype, n) for co in (3 * c, c, mlp.fc1.out_features)))
+        return self._param_cache().get(
+            ("expand", dtype), [up.weight, lin.weight],
+            lambda: fold_expand(up.weight.detach().float(), lin.weight.detach().float()).to(dtype).contiguous())
 
     def cpe_rows(self, spt):
         """cpe[0..7] in eval: the (N, C) rows in front of the last LayerNorm.  Reads the sparse tensor's features, as the
@@ -175,74 +147,10 @@ class BlockPlus(PointModule):
             h = ops.affine_act(ops.layernorm(h, g4, b4, c[4].eps), None, None, ops.ACT_RELU)
         return ops.gemm(h, self.expand_weight(dt), bias=c[7].bias_f32())
 
-    def _forward_eval(self, point: Point):
-        """Fused eval: the bottleneck CPE, then Block's dispatch from the conv output on (the same entry points behind
-        the same capability checks: ptv3_block_head / _tail, ptv3_rows_linear, ptv3_layernorm)."""
-        mlp = self.mlp[0]
-        spt = point.sparse_conv_feat
-        dt = spt.features.dtype
-        shortcut = point.feat
-        x = self.cpe_rows(spt)
-        g0, b0 = self.cpe[8].affine_f32()
-        g1, b1 = self.norm1[0].affine_f32()
-        eps = self.cpe[8].eps
-        same_eps = eps == self.norm1[0].eps == self.norm2[0].eps
-        if (ops.block_fusable(self.channels, mlp.fc1.out_features, dt, shortcut.shape[0])
-                and isinstance(mlp.act, nn.GELU) and same_eps and self.attn.qkv.bias is not None):
-            wqkv, wproj, w1, w2 = self.chain_weights(dt)
-            g2, b2 = self.norm2[0].affine_f32()
-            f1, qkv = ops.block_head(x, None, 0, None, shortcut, g0, b0, g1, b1, wqkv, self.attn.qkv.bias_f32(), eps)
-            x = self.attn.attention_core(point, qkv)
-            feat = ops.block_tail(x, f1, wproj, self.attn.proj.bias_f32(), g2, b2, w1, mlp.fc1.bias_f32(), w2,
-                                  mlp.fc2.bias_f32(), eps)
-        else:
-            rows = self._rows_path(shortcut)
-            if rows:
-                feat, qkv = ops.rows_linear(x, self.attn.qkv.weight_for(dt), self.attn.qkv.bias_f32(), ln=(g1, b1),
-                                            ln0=(g0, b0), shortcut=shortcut, eps=eps)
-            else:
-                feat, x = ops.layernorm(x, g0, b0, eps, res=shortcut, gamma2=g1, beta2=b1)
-                qkv = self.attn.qkv(x)
-            x = self.attn.attention_core(point, qkv)
-            if rows:
-                feat = ops.rows_linear(x, self.attn.proj.weight_for(dt), self.attn.proj.bias_f32(), res=feat)
-                g3, b3 = self.norm2[0].affine_f32()
-                h = ops.rows_linear(feat, mlp.fc1.weight_for(dt), mlp.fc1.bias_f32(), act=ops.ACT_GELU, ln=(g3, b3),
-                                    eps=self.norm2[0].eps)
-                feat = mlp.fc2(h, res=feat)
-            else:
-                feat = self.attn.proj(x, res=feat)
-                feat = mlp(self.norm2[0](feat), res=feat)
-        point.feat = feat
-        point.sparse_conv_feat = spt.replace_feature(feat)
-        return point
-
     def forward(self, point: Point):
         if self.training or not self.fused or not self._fusable():
             return self._forward_generic(point)
-        return self._forward_eval(point)
-
-    def _forward_generic(self, point: Point):
-        """The reference's statement order (:125-153) on the unfused layer ops; DropPath as in Block's generic path."""
-        shortcut = point.feat
-        point = self.cpe(point)
-        point.feat = _add(shortcut, point.feat)
-        shortcut = point.feat
-        if self.pre_norm:
-            point = self.norm1(point)
-        point = self.drop_path(self.attn(point))
-        point.feat = _add(shortcut, point.feat)
-        if not self.pre_norm:
-            point = self.norm1(point)
-        shortcut = point.feat
-        if self.pre_norm:
-            point = self.norm2(point)
-        point = self.drop_path(self.mlp(point))
-        point.feat = _add(shortcut, point.feat)
-        if not self.pre_norm:
-            point = self.norm2(point)
-        point.sparse_conv_feat = point.sparse_conv_feat.replace_feature(point.feat)
-        return point
+        return self._eval_after_cpe(point, x=self.cpe_rows(point.sparse_conv_feat))
 
 
 AXIS_PERMUTATIONS = {1: [1, 2, 0], 2: [2, 0, 1]}   # s % 3 -> YZX, ZXY (:391-396); 0: no reorder
@@ -392,11 +300,7 @@ class PointTransformerV3Plus(PointModule):
         check_sync_batchnorm(self)
         with torch.set_grad_enabled(self.training and torch.is_grad_enabled()):
             point = Point(data_dict)
-            dtype = self.resolve_dtype()
-            feat = point.feat
-            if feat.dtype not in (torch.float32, torch.bfloat16):
-                feat = feat.float()
-            point.feat = ops.cast(feat.contiguous(), dtype)
+            point.feat = _input_feat(point.feat, self.resolve_dtype())
             point.serialization(order=self.order, shuffle_orders=self.shuffle_orders)
             point.sparsify()
             point = self.embedding(point)

@@ -218,15 +218,11 @@ class Block(PointModule):
     def __init__(self, channels, num_heads, patch_size=48, mlp_ratio=4.0, qkv_bias=True, qk_scale=None,
                  attn_drop=0.0, proj_drop=0.0, drop_path=0.0, norm_layer=LayerNorm, act_layer=GELU,
                  pre_norm=True, order_index=0, cpe_indice_key=None, enable_rpe=False, enable_flash=True,
-                 upcast_attention=True, upcast_softmax=True):
+                 upcast_attention=True, upcast_softmax=True, **cpe_args):
         super().__init__()
         self.channels = channels
         self.pre_norm = pre_norm
-        self.cpe = PointSequential(
-            SubMConv3d(channels, channels, kernel_size=3, bias=True, indice_key=cpe_indice_key),
-            Linear(channels, channels),
-            norm_layer(channels),
-        )
+        self.cpe = self._build_cpe(channels, norm_layer, cpe_indice_key, **cpe_args)
         self.norm1 = PointSequential(norm_layer(channels))
         self.attn = SerializedAttention(
             channels=channels, patch_size=patch_size, num_heads=num_heads, qkv_bias=qkv_bias,
@@ -237,6 +233,16 @@ class Block(PointModule):
         self.mlp = PointSequential(MLP(in_channels=channels, hidden_channels=int(channels * mlp_ratio),
                                        out_channels=channels, act_layer=act_layer, drop=proj_drop))
         self.drop_path = PointSequential(DropPath(drop_path) if drop_path > 0.0 else nn.Identity())
+
+    @staticmethod
+    def _build_cpe(channels, norm_layer, indice_key):
+        """the xCPE (:277-285); a subclass with another CPE overrides this, so only one is ever drawn.  Its last module is
+        the LayerNorm in front of the first residual add."""
+        return PointSequential(
+            SubMConv3d(channels, channels, kernel_size=3, bias=True, indice_key=indice_key),
+            Linear(channels, channels),
+            norm_layer(channels),
+        )
 
     def _fusable(self):
         return (self.pre_norm and isinstance(self.cpe[2], LayerNorm) and isinstance(self.norm1[0], LayerNorm)
@@ -249,15 +255,18 @@ class Block(PointModule):
         mlp = self.mlp[0]
         n, c = feat.shape
         return (n >= ops.rows_linear_rows() and isinstance(mlp.act, nn.GELU) and self.attn.qkv.bias is not None
-                and self.cpe[2].eps == self.norm1[0].eps == self.norm2[0].eps
+                and self.cpe[-1].eps == self.norm1[0].eps == self.norm2[0].eps
                 and all(ops.rows_linear_capable(c, co, feat.dtype, n) for co in (3 * c, c, mlp.fc1.out_features)))
+
+    def _param_cache(self):
+        """derived weights (folded, cast, permuted), rebuilt when a source parameter's version changes"""
+        return self.__dict__.setdefault("_fold_cache", _ParamCache())
 
     def folded_cpe(self, dtype):
         """xCPE conv followed by its Linear (:277-285) has no nonlinearity in between, so the Linear is folded
         into the 27 kernel taps once per weight version:  W'_d = W_lin @ W_d,  b' = W_lin @ b_conv + b_lin.
         Saves one GEMM launch and one (N, C) round trip per block; fp32 reassociation only."""
         conv, lin = self.cpe[0], self.cpe[1]
-        cache = self.__dict__.setdefault("_fold_cache", _ParamCache())
 
         def make():
             wc = conv.weight.detach().float().reshape(conv.out_channels, -1, conv.in_channels)
@@ -265,13 +274,12 @@ class Block(PointModule):
             w = torch.einsum("oc,ckd->okd", wl, wc).reshape(lin.out_features, -1)
             b = wl @ conv.bias.detach().float() + lin.bias.detach().float()
             return w.to(dtype).contiguous(), b.contiguous()
-        return cache.get(("cpe", dtype), [conv.weight, conv.bias, lin.weight, lin.bias], make)
+        return self._param_cache().get(("cpe", dtype), [conv.weight, conv.bias, lin.weight, lin.bias], make)
 
     def chain_weights(self, dtype):
         """(qkv, proj, fc1, fc2) weight matrices in `dtype`; the three GEMMs fed from registers by the fused block
         kernels get their input channels permuted (ops.chain_permute), once per weight version."""
         mlp = self.mlp[0]
-        cache = self.__dict__.setdefault("_fold_cache", _ParamCache())
 
         def make():
             cast = lambda w: w.detach().to(dtype).contiguous()  # noqa: E731
@@ -279,33 +287,53 @@ class Block(PointModule):
                     if ops.block_fusable(self.channels, mlp.fc1.out_features, dtype) == 1 else (lambda w: w))
             return (perm(cast(self.attn.qkv.weight)), cast(self.attn.proj.weight),
                     perm(cast(mlp.fc1.weight)), perm(cast(mlp.fc2.weight)))
-        return cache.get(("chain", dtype), [self.attn.qkv.weight, self.attn.proj.weight, mlp.fc1.weight,
-                                            mlp.fc2.weight], make)
+        return self._param_cache().get(("chain", dtype), [self.attn.qkv.weight, self.attn.proj.weight, mlp.fc1.weight,
+                                                          mlp.fc2.weight], make)
 
-    def _forward_fused_kernels(self, point: Point):
-        """conv -> block_head -> window attention -> block_tail: 4 launches."""
-        mlp = self.mlp[0]
-        spt = point.sparse_conv_feat
-        dtype = spt.features.dtype
-        wf, bf = self.folded_cpe(dtype)
-        wqkv, wproj, w1, w2 = self.chain_weights(dtype)
-        nbr = spt.neighbors(3, self.cpe[0].indice_key)
-        g0, b0 = self.cpe[2].affine_f32()
+    def _eval_after_cpe(self, point: Point, x=None, slabs=None, conv_bias=None):
+        """Eval, from the CPE's linear part to the end of the block.  The rows in front of the CPE's last LayerNorm come
+        as `x` (N, C), or still as the split-K `slabs` of ops.conv_slabs with their `conv_bias`.  The branches are the
+        executor's (csrc/engine.hip): the fused halves where ptv3_block_fusable serves the shape (conv -> block_head ->
+        window attention -> block_tail: 4 launches), else residual adds and norms folded into the epilogues of
+        ptv3_layernorm[_slabs] + GEMMs, or of ptv3_rows_linear where _rows_path says so (9 launches)."""
+        mlp, qkv_lin, norm2 = self.mlp[0], self.attn.qkv, self.norm2[0]
+        shortcut = point.feat
+        n, dt = shortcut.shape[0], shortcut.dtype
+        g0, b0 = self.cpe[-1].affine_f32()
         g1, b1 = self.norm1[0].affine_f32()
-        g2, b2 = self.norm2[0].affine_f32()
-        eps = self.cpe[2].eps
-        slabs = ops.conv_slabs(spt.features, wf, nbr, 27, spt.row_order)
-        if slabs is not None:
-            f1, qkv = ops.block_head(None, slabs[0], slabs[1], bf, point.feat, g0, b0, g1, b1, wqkv,
-                                     self.attn.qkv.bias_f32(), eps)
+        g2, b2 = norm2.affine_f32()
+        eps = self.cpe[-1].eps
+        if (ops.block_fusable(self.channels, mlp.fc1.out_features, dt, n) and isinstance(mlp.act, nn.GELU)
+                and eps == self.norm1[0].eps == norm2.eps and qkv_lin.bias is not None):   # the head reads bqkv
+            wqkv, wproj, w1, w2 = self.chain_weights(dt)
+            slab, splits = slabs if slabs is not None else (None, 0)
+            f1, qkv = ops.block_head(x, slab, splits, conv_bias, shortcut, g0, b0, g1, b1, wqkv, qkv_lin.bias_f32(), eps)
+            x = self.attn.attention_core(point, qkv)
+            feat = ops.block_tail(x, f1, wproj, self.attn.proj.bias_f32(), g2, b2, w1, mlp.fc1.bias_f32(), w2,
+                                  mlp.fc2.bias_f32(), eps)
         else:
-            x = ops.gemm(spt.features, wf, bias=bf, nbr=nbr, kvol=27, row_order=spt.row_order)
-            f1, qkv = ops.block_head(x, None, 0, None, point.feat, g0, b0, g1, b1, wqkv, self.attn.qkv.bias_f32(), eps)
-        x = self.attn.attention_core(point, qkv)
-        feat = ops.block_tail(x, f1, wproj, self.attn.proj.bias_f32(), g2, b2, w1, mlp.fc1.bias_f32(), w2,
-                              mlp.fc2.bias_f32(), eps)
+            rows = self._rows_path(shortcut)
+            if slabs is not None:   # deep levels: the conv splits over K; the LayerNorm kernel sums the slabs
+                feat, x = ops.layernorm_slabs(slabs[0], slabs[1], n, self.channels, conv_bias, dt, g0, b0, eps,
+                                              res=shortcut, gamma2=g1, beta2=b1)
+                qkv = qkv_lin(x)
+            elif rows:
+                feat, qkv = ops.rows_linear(x, qkv_lin.weight_for(dt), qkv_lin.bias_f32(), ln=(g1, b1), ln0=(g0, b0),
+                                            shortcut=shortcut, eps=eps)
+            else:
+                feat, x = ops.layernorm(x, g0, b0, eps, res=shortcut, gamma2=g1, beta2=b1)
+                qkv = qkv_lin(x)
+            x = self.attn.attention_core(point, qkv)
+            if rows:
+                feat = ops.rows_linear(x, self.attn.proj.weight_for(dt), self.attn.proj.bias_f32(), res=feat)
+                h = ops.rows_linear(feat, mlp.fc1.weight_for(dt), mlp.fc1.bias_f32(), act=ops.ACT_GELU, ln=(g2, b2),
+                                    eps=eps)
+                feat = mlp.fc2(h, res=feat)
+            else:
+                feat = self.attn.proj(x, res=feat)                  # + shortcut
+                feat = mlp(norm2(feat), res=feat)                   # fc1+GELU, fc2 + shortcut
         point.feat = feat
-        point.sparse_conv_feat = spt.replace_feature(feat)
+        point.sparse_conv_feat = point.sparse_conv_feat.replace_feature(feat)
         return point
 
     def _train_fusable(self):
@@ -363,47 +391,14 @@ class Block(PointModule):
             return self._forward_train(point)
         if self.training or not self._fusable():
             return self._forward_generic(point)
-        mlp = self.mlp[0]
-        if (ops.block_fusable(self.channels, mlp.fc1.out_features, point.feat.dtype, point.feat.shape[0]) and isinstance(mlp.act, nn.GELU)
-                and self.cpe[2].eps == self.norm1[0].eps == self.norm2[0].eps):
-            return self._forward_fused_kernels(point)
-        # ---- fused eval path: 9 launches per block, residual adds and norms folded into epilogues
-        shortcut = point.feat
         spt = point.sparse_conv_feat                         # xCPE conv reads the sparse tensor's features
         wf, bf = self.folded_cpe(spt.features.dtype)
         nbr = spt.neighbors(3, self.cpe[0].indice_key)
-        g1, b1 = self.cpe[2].affine_f32()
-        g2, b2 = self.norm1[0].affine_f32()
         slabs = ops.conv_slabs(spt.features, wf, nbr, 27, spt.row_order)
-        # whole-row linears with their LayerNorms folded in (ptv3_rows_linear; the executor takes the same branches)
-        rows = self._rows_path(point.feat)
-        dt = spt.features.dtype
-        if slabs is not None:   # deep levels: the conv splits over K; the LayerNorm kernel sums the slabs
-            feat, x = ops.layernorm_slabs(slabs[0], slabs[1], nbr.shape[0], wf.shape[0], bf, spt.features.dtype, g1, b1,
-                                          self.cpe[2].eps, res=shortcut, gamma2=g2, beta2=b2)
-            qkv = self.attn.qkv(x)
-        elif rows:
-            x = ops.gemm(spt.features, wf, bias=bf, nbr=nbr, kvol=27, row_order=spt.row_order)
-            feat, qkv = ops.rows_linear(x, self.attn.qkv.weight_for(dt), self.attn.qkv.bias_f32(), ln=(g2, b2), ln0=(g1, b1),
-                                        shortcut=shortcut, eps=self.cpe[2].eps)
-        else:
-            x = ops.gemm(spt.features, wf, bias=bf, nbr=nbr, kvol=27, row_order=spt.row_order)
-            feat, x = ops.layernorm(x, g1, b1, self.cpe[2].eps, res=shortcut, gamma2=g2, beta2=b2)
-            qkv = self.attn.qkv(x)
-        x = self.attn.attention_core(point, qkv)
-        if rows:
-            feat = ops.rows_linear(x, self.attn.proj.weight_for(dt), self.attn.proj.bias_f32(), res=feat)
-            g3, b3 = self.norm2[0].affine_f32()
-            h = ops.rows_linear(feat, mlp.fc1.weight_for(dt), mlp.fc1.bias_f32(), act=ops.ACT_GELU, ln=(g3, b3),
-                                eps=self.norm2[0].eps)
-            feat = mlp.fc2(h, res=feat)
-        else:
-            feat = self.attn.proj(x, res=feat)                  # + shortcut
-            x = self.norm2[0](feat)
-            feat = self.mlp[0](x, res=feat)                     # fc1+GELU, fc2 + shortcut
-        point.feat = feat
-        point.sparse_conv_feat = point.sparse_conv_feat.replace_feature(feat)
-        return point
+        if slabs is not None:
+            return self._eval_after_cpe(point, slabs=slabs, conv_bias=bf)
+        x = ops.gemm(spt.features, wf, bias=bf, nbr=nbr, kvol=27, row_order=spt.row_order)
+        return self._eval_after_cpe(point, x=x)
 
     def _forward_generic(self, point: Point):
         """The reference's statement order (:318-338) on the unfused layer ops."""
@@ -661,6 +656,15 @@ class Embedding(PointModule):
         return self.stem(point)
 
 
+def _input_feat(feat, dtype):
+    """a backbone's input features as the kernels take them: fp32 unless already fp32 / bf16, contiguous, and cast to
+    `dtype` (None: left to the callee)"""
+    if feat.dtype not in (torch.float32, torch.bfloat16):
+        feat = feat.float()
+    feat = feat.contiguous()
+    return feat if dtype is None else ops.cast(feat, dtype)
+
+
 @MODELS.register_module("PT-v3m1")
 class PointTransformerV3(PointModule):
     def __init__(
@@ -828,11 +832,8 @@ class PointTransformerV3(PointModule):
                 data_dict["_batch_pending"] = True
             point = Point(data_dict)
             dtype = self.resolve_dtype()
-            feat = point.feat
-            if feat.dtype not in (torch.float32, torch.bfloat16):
-                feat = feat.float()
             overlap = use_engine and self.overlap_calls and self.inputs_resident
-            point.feat = feat.contiguous() if overlap else ops.cast(feat.contiguous(), dtype)
+            point.feat = _input_feat(point.feat, None if overlap else dtype)
             if use_engine:
                 point._ensure_grid_coord()
                 point, head_out = _engine.forward(self, point, dtype, _head)

@@ -37,6 +37,24 @@ def test_names_registered_and_reference_module_path_imports():
             raise AssertionError(f"{bad}=True must raise")
 
 
+def test_block_plus_is_a_block_with_unchanged_construction():
+    """BlockPlus subclasses Block but keeps its own class name (the native executor matches on "Block"), and building
+    either backbone draws from the RNG as before the two classes were joined: float64 sum of |p| over all parameters
+    after torch.manual_seed(0), recorded at the commit before (CPU initialisation is deterministic)."""
+    from pointcept.models import build_model, BlockPlus
+    from pointcept.models.point_transformer_v3.point_transformer_v3m1_base import Block
+    from make_golden_cfg import TINY_CFG
+    assert issubclass(BlockPlus, Block)
+    for cfg, expected in ((dict(type="PT-v3m1-Plus", **PLUS_TINY_CFG), 27887.581024057035),
+                          (dict(type="PT-v3m1", **TINY_CFG), 16141.89209908651)):
+        torch.manual_seed(0)
+        model = build_model(cfg)
+        total = sum(p.detach().double().abs().sum().item() for p in model.parameters())
+        assert abs(total - expected) <= 1e-12 * expected, (cfg["type"], repr(total))
+        names = {type(m).__name__ for m in model.modules() if isinstance(m, Block)}
+        assert names == ({"BlockPlus"} if cfg["type"] == "PT-v3m1-Plus" else {"Block"})
+
+
 def test_fork_config_builds_with_reference_state_dict(golden_dir):
     """configs/my_dataset/keypoint_ptv3_plus.py through the registry: keys, shapes, dtypes and order of the reference
     class built from the same config (tests/golden/make_golden_keypoint_ptv3_plus.py)."""
