@@ -132,6 +132,17 @@ int ptv3_subm_build_table(const int32_t* indices, int64_t n, void* table, int64_
 int ptv3_subm_neighbors(const int32_t* indices, int64_t n, const void* table, int64_t slots, int ksize,
                         int32_t* nbr, void* stream);
 
+/* The same neighbour table (bitwise the one the full-probing form of ptv3_subm_neighbors gives, duplicate rows
+ * included: the smallest row of a coordinate wins, the centre tap is the row itself) from a hash of the occupied
+ * 4 x 4 x 4 BLOCKS of sites: a block's slot (key, 64-bit occupancy mask, payload base) and its rows share cache
+ * lines among all the taps that fall into it, where the per-site table costs a line per probed voxel.
+ * table: ptv3_subm_block_table_bytes(n) bytes, 16-byte aligned, opaque; build it once per set of sites and query it
+ * for any ksize in {1, 3, 5, 7} with the same indices and n.  Every entry of nbr is written (no pre-fill needed). */
+size_t ptv3_subm_block_table_bytes(int64_t n);
+int ptv3_subm_build_block_table(const int32_t* indices, int64_t n, void* table, size_t bytes, void* stream);
+int ptv3_subm_neighbors_blocks(const int32_t* indices, int64_t n, const void* table, size_t bytes, int ksize,
+                               int32_t* nbr, void* stream);
+
 /* y = epilogue( sum_{d<kvol} sum_{c<cin} w[o][d][c] * x[nbr[i][d]][c] ).
  *   nbr == NULL, kvol == 1  ->  plain torch.nn.Linear: y = x @ w^T            (w: (cout, cin))
  *   nbr != NULL             ->  spconv SubMConv3d, w: (cout, k,k,k, cin) = (cout, kvol, cin)

@@ -94,7 +94,7 @@ struct Level {
   const int64_t* offset = nullptr;
   const int64_t* grid = nullptr; const int64_t* batch = nullptr;
   int64_t *code = nullptr, *order = nullptr, *inverse = nullptr;
-  int32_t* indices = nullptr; void* table = nullptr; int64_t slots = 0;
+  int32_t* indices = nullptr; void* table = nullptr; size_t table_bytes = 0;   // table of 4^3 blocks (sparse.hip)
   int32_t* nbr3 = nullptr; int32_t* nbr5 = nullptr; int32_t* row_order = nullptr;
   Plan plan[2];                 // [0] encoder patch, [1] decoder patch (shared when K is equal)
   int32_t* seg = nullptr;       // runs of THIS level's points in order 0 that form the next level's rows
@@ -275,17 +275,19 @@ struct Run {
     if (!dry && ok())
       hipLaunchKernelGGL(make_indices_kernel, dim3((unsigned)cdiv(L.n, 256)), dim3(256), 0, sg, L.batch, grid_in, is_i64,
                          L.n, L.indices, g64, L.row_order, L.order);
-    L.slots = ptv3_subm_table_slots(L.n);
-    L.table = G->alloc((size_t)L.slots * 12);
-    RUN(ptv3_subm_build_table(L.indices, L.n, L.table, L.slots, sg));
+    // neighbour tables through the block table at every level: its kernels write whole rows (no -1 pre-fill) and touch
+    // a fifth of the lines of the per-voxel probes, which headed the forward's critical path at the 5^3 stem
+    L.table_bytes = ptv3_subm_block_table_bytes(L.n);
+    L.table = G->alloc(L.table_bytes);
+    RUN(ptv3_subm_build_block_table(L.indices, L.n, L.table, L.table_bytes, sg));
     if (st == 0) {
       L.nbr5 = (int32_t*)G->alloc((size_t)L.n * 125 * 4);
-      RUN(ptv3_subm_neighbors(L.indices, L.n, L.table, L.slots, 5, L.nbr5, sg));
+      RUN(ptv3_subm_neighbors_blocks(L.indices, L.n, L.table, L.table_bytes, 5, L.nbr5, sg));
       // the stem conv needs the 5^3 table and the row order only: it starts here, under the 3^3 table and the window plans
       if (!dry && ok() && stem_ready) (void)hipEventRecord(stem_ready, sg);
     }
     L.nbr3 = (int32_t*)G->alloc((size_t)L.n * 27 * 4);
-    RUN(ptv3_subm_neighbors(L.indices, L.n, L.table, L.slots, 3, L.nbr3, sg));
+    RUN(ptv3_subm_neighbors_blocks(L.indices, L.n, L.table, L.table_bytes, 3, L.nbr3, sg));
     const int Ke = patch_K(L, d->enc_patch[st]);
     window_plan(L, L.plan[0], Ke);
     if (!d->enc_mode && st < d->num_stages - 1) {

@@ -85,6 +85,161 @@ __global__ void ht_neighbors_half_kernel(const int32_t* __restrict__ idx, int64_
   }
 }
 
+// ---- neighbour tables from a table of 4 x 4 x 4 blocks (hashtable.h) ---------------------------------------------
+// The per-voxel probes above cost one 128-byte line per probed voxel (89 distinct lines per site at 5^3 on the 100k
+// surface scene); a k^3 neighbourhood with k <= 5 lies in at most 8 blocks, whose slot and payload lines serve all of
+// its taps (16 lines per site on the same scene).  Table memory of n sites, S = ptv3_subm_table_slots(n):
+//   S x BlockSlot | payload: n x uint32 | counter (16 bytes) | site_slot: n x int32
+// payload holds ~row (0 = never written, every ~row has bit 31 set), so one zero fill initialises slots, payload and
+// counter, and "smallest row wins" among duplicate coordinates is an atomicMax.
+struct BlockTable {
+  BlockSlot* slots; uint32_t* payload; int32_t* counter; int32_t* site_slot; uint64_t smask; size_t zero_bytes;
+};
+static inline size_t bt_payload_bytes(int64_t n) { return ((size_t)n * 4 + 15) & ~(size_t)15; }
+static inline BlockTable bt_layout(void* table, int64_t n) {
+  const int64_t S = ptv3_subm_table_slots(n);
+  char* p = (char*)table;
+  BlockTable t;
+  t.slots = (BlockSlot*)p;
+  t.payload = (uint32_t*)(p + (size_t)S * sizeof(BlockSlot));
+  t.counter = (int32_t*)((char*)t.payload + bt_payload_bytes(n));
+  t.site_slot = (int32_t*)((char*)t.counter + 16);
+  t.smask = (uint64_t)(S - 1);
+  t.zero_bytes = (size_t)S * sizeof(BlockSlot) + bt_payload_bytes(n) + 16;
+  return t;
+}
+
+// every site claims its block's slot and sets its voxel's bit; the slot is kept for bt_payload_kernel
+__global__ void bt_claim_kernel(const int32_t* __restrict__ idx, int64_t n, BlockSlot* slots, uint64_t smask,
+                                int32_t* __restrict__ site_slot) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int4 s = reinterpret_cast<const int4*>(idx)[i];
+  const uint64_t key = block_key(s.x, s.y >> 2, s.z >> 2, s.w >> 2);
+  uint64_t slot = mix64(key) & smask;
+  int32_t mine = -1;                       // stays -1 only if the table were full (slots >= 2n: it never is)
+  for (uint64_t probe = 0; probe <= smask; ++probe) {
+    const unsigned long long prev = atomicCAS(&slots[slot].key, 0ull, (unsigned long long)key);
+    if (prev == 0 || prev == key) {
+      atomicOr(&slots[slot].mask, 1ull << block_bit(s.y, s.z, s.w));
+      mine = (int32_t)slot;
+      break;
+    }
+    slot = (slot + 1) & smask;
+  }
+  site_slot[i] = mine;
+}
+
+// payload ranges: a workgroup takes 1024 slots, four per lane, and one atomicAdd for all of them (one per wave was
+// 4096 returning atomics on one address at 100k sites: 43 us).  The order of the ranges is free: nbr does not depend
+// on it.  The grid covers the slots exactly (a power of two >= 1024).
+__global__ __launch_bounds__(256) void bt_base_kernel(BlockSlot* slots, int32_t* counter) {
+  __shared__ int s_wave[4];
+  __shared__ int s_start;
+  const int64_t s0 = (int64_t)blockIdx.x * 1024 + threadIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int cnt[4], mine = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { cnt[j] = __popcll(slots[s0 + j * 256].mask); mine += cnt[j]; }
+  int incl = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int up = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    s_start = total ? atomicAdd(counter, total) : 0;
+  }
+  __syncthreads();
+  int at = s_start + incl - mine;
+  for (int w = 0; w < wave; ++w) at += s_wave[w];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (cnt[j]) slots[s0 + j * 256].base = at;
+    at += cnt[j];
+  }
+}
+
+__global__ void bt_payload_kernel(const int32_t* __restrict__ idx, int64_t n, const BlockSlot* __restrict__ slots,
+                                  const int32_t* __restrict__ site_slot, uint32_t* payload) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t slot = site_slot[i];
+  if (slot < 0) return;
+  const int4 s = reinterpret_cast<const int4*>(idx)[i];
+  const unsigned long long m = slots[slot].mask;
+  const int bit = block_bit(s.y, s.z, s.w);
+  // the ranges of bt_base_kernel are disjoint and sum to the number of distinct voxels (<= n), and this site's bit is
+  // set in m: base + rank < n
+  const int at = slots[slot].base + __popcll(m & ((1ull << bit) - 1));
+  atomicMax(&payload[at], ~(uint32_t)i);   // duplicate coordinates keep the smallest row, as ht_insert_kernel does
+}
+
+// A workgroup serves SITES consecutive sites: its first lanes resolve the candidate blocks of each site once (NB per
+// axis: a span of k voxels touches 2 blocks for k <= 5, 3 for k = 7), then all lanes walk the SITES * k^3 entries of
+// the output in order - every entry is written exactly once, in coalesced rows, -1 included: no pre-fill.  A payload
+// index is base + rank of a slot whose key matched and whose bit is set, so it is < n by the invariant above.
+template <int K, int SITES>
+__global__ __launch_bounds__(256) void bt_neighbors_kernel(const int32_t* __restrict__ idx, int64_t n,
+                                                           const BlockSlot* __restrict__ slots, uint64_t smask,
+                                                           const uint32_t* __restrict__ payload,
+                                                           int32_t* __restrict__ nbr) {
+  constexpr int KVOL = K * K * K, H = K / 2, NB = K <= 5 ? 2 : 3, NC = NB * NB * NB;
+  constexpr int ITER = (SITES * KVOL + 255) / 256;
+  __shared__ int4 s_site[SITES];
+  __shared__ unsigned long long s_mask[SITES * NC];
+  __shared__ int32_t s_base[SITES * NC];
+  const int64_t i0 = (int64_t)blockIdx.x * SITES;
+  for (int c = threadIdx.x; c < SITES * NC; c += 256) {
+    const int s = c / NC, cc = c - s * NC;
+    unsigned long long m = 0;
+    int32_t base = 0;
+    if (i0 + s < n) {
+      const int4 p = reinterpret_cast<const int4*>(idx)[i0 + s];
+      if (cc == 0) s_site[s] = p;
+      const int cx = cc / (NB * NB), cy = (cc / NB) % NB, cz = cc % NB;
+      const int bx0 = (p.y - H) >> 2, by0 = (p.z - H) >> 2, bz0 = (p.w - H) >> 2;   // -1 at the lower bound
+      const int bx = bx0 + cx, by = by0 + cy, bz = bz0 + cz;
+      if (bx >= 0 && by >= 0 && bz >= 0 && bx <= ((p.y + H) >> 2) && by <= ((p.z + H) >> 2) &&
+          bz <= ((p.w + H) >> 2) && bx < 16384 && by < 16384 && bz < 16384) {
+        const int64_t slot = bt_find(slots, smask, p.x, bx, by, bz);
+        if (slot >= 0) { m = slots[slot].mask; base = slots[slot].base; }
+      }
+    }
+    s_mask[c] = m;
+    s_base[c] = base;
+  }
+  __syncthreads();
+  int32_t v[ITER];
+#pragma unroll
+  for (int it = 0; it < ITER; ++it) {
+    const int t = threadIdx.x + it * 256;
+    const int s = t / KVOL, d = t - s * KVOL;
+    v[it] = -1;
+    if (t < SITES * KVOL && i0 + s < n) {
+      const int4 p = s_site[s];
+      const int x = p.y + d / (K * K) - H, y = p.z + (d / K) % K - H, z = p.w + d % K - H;
+      if (d == KVOL / 2) {
+        v[it] = (int32_t)(i0 + s);   // the centre tap is the site itself
+      } else if (x >= 0 && y >= 0 && z >= 0 && x < 65536 && y < 65536 && z < 65536) {
+        const int c = s * NC + (((x >> 2) - ((p.y - H) >> 2)) * NB + ((y >> 2) - ((p.z - H) >> 2))) * NB +
+                      ((z >> 2) - ((p.w - H) >> 2));
+        const unsigned long long m = s_mask[c];
+        const int bit = block_bit(x, y, z);
+        if ((m >> bit) & 1) v[it] = (int32_t)~payload[s_base[c] + __popcll(m & ((1ull << bit) - 1))];
+      }
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < ITER; ++it) {
+    const int t = threadIdx.x + it * 256;
+    if (t < SITES * KVOL && i0 + t / KVOL < n) nbr[i0 * KVOL + t] = v[it];
+  }
+}
+
 }  // namespace ptv3
 
 using namespace ptv3;
@@ -136,6 +291,61 @@ extern "C" int ptv3_subm_neighbors(const int32_t* indices, int64_t n, const void
     while ((1 << sl) < kvol / 2 + 1) ++sl;          // 1: 0, 3^3: 4, 5^3: 6, 7^3: 8
     hipLaunchKernelGGL(ht_neighbors_half_kernel, dim3((unsigned)cdiv(n, 256 >> sl)), dim3(256), 0,
                        (hipStream_t)stream, indices, n, keys, vals, (uint64_t)(slots - 1), ksize, kvol, sl, nbr);
+  }
+  PTV3_LAUNCH_CHECK();
+  return PTV3_OK;
+}
+
+extern "C" size_t ptv3_subm_block_table_bytes(int64_t n) {
+  if (n < 0) n = 0;
+  return (size_t)ptv3_subm_table_slots(n) * sizeof(BlockSlot) + 2 * bt_payload_bytes(n) + 16;
+}
+
+extern "C" int ptv3_subm_build_block_table(const int32_t* indices, int64_t n, void* table, size_t bytes,
+                                           void* stream) {
+  PTV3_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "subm_build_block_table: n=%lld out of range", (long long)n);
+  PTV3_REQUIRE(table && bytes >= ptv3_subm_block_table_bytes(n) && ((uintptr_t)table & 15) == 0,
+               "subm_build_block_table: table must be 16-byte aligned and hold ptv3_subm_block_table_bytes(n) bytes");
+  PTV3_REQUIRE(n == 0 || indices, "subm_build_block_table: indices are required");
+  hipStream_t s = (hipStream_t)stream;
+  const BlockTable t = bt_layout(table, n);
+  if (hipMemsetAsync(table, 0, t.zero_bytes, s) != hipSuccess) {
+    set_error("subm_build_block_table: memset failed");
+    return PTV3_ERR_LAUNCH;
+  }
+  if (n == 0) return PTV3_OK;
+  const dim3 sites((unsigned)cdiv(n, 256)), block(256);
+  hipLaunchKernelGGL(bt_claim_kernel, sites, block, 0, s, indices, n, t.slots, t.smask, t.site_slot);
+  hipLaunchKernelGGL(bt_base_kernel, dim3((unsigned)((t.smask + 1) / 1024)), block, 0, s, t.slots, t.counter);
+  hipLaunchKernelGGL(bt_payload_kernel, sites, block, 0, s, indices, n, t.slots, t.site_slot, t.payload);
+  PTV3_LAUNCH_CHECK();
+  return PTV3_OK;
+}
+
+template <int K, int SITES>
+static void bt_neighbors_launch(const int32_t* indices, int64_t n, const BlockTable& t, int32_t* nbr, hipStream_t s) {
+  hipLaunchKernelGGL((bt_neighbors_kernel<K, SITES>), dim3((unsigned)cdiv(n, SITES)), dim3(256), 0, s, indices, n,
+                     t.slots, t.smask, t.payload, nbr);
+}
+
+extern "C" int ptv3_subm_neighbors_blocks(const int32_t* indices, int64_t n, const void* table, size_t bytes,
+                                          int ksize, int32_t* nbr, void* stream) {
+  PTV3_REQUIRE(ksize >= 1 && ksize <= 7 && (ksize & 1), "subm_neighbors_blocks: ksize %d must be odd and <= 7", ksize);
+  PTV3_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "subm_neighbors_blocks: n=%lld out of range", (long long)n);
+  PTV3_REQUIRE(table && bytes >= ptv3_subm_block_table_bytes(n) && ((uintptr_t)table & 15) == 0,
+               "subm_neighbors_blocks: table must be the one ptv3_subm_build_block_table built for these n sites");
+  if (n == 0) return PTV3_OK;
+  PTV3_REQUIRE(indices && nbr, "subm_neighbors_blocks: indices and nbr are required");
+  const BlockTable t = bt_layout(const_cast<void*>(table), n);
+  hipStream_t s = (hipStream_t)stream;
+  // sites per workgroup: several independent payload reads per lane and a wave or more of block lookups; measured
+  // flat around these at 100k sites (5^3: 40.0 / 34.2 / 33.5 / 36.4 us at 4 / 8 / 16 / 32 sites; 3^3: 12.3 / 12.1 /
+  // 13.4 / 16.2 us at 16 / 32 / 64 / 128), the smaller choice keeps the deeper levels' few thousand sites spread out
+  switch (ksize) {
+    case 1: bt_neighbors_launch<1, 256>(indices, n, t, nbr, s); break;
+    case 3: bt_neighbors_launch<3, 16>(indices, n, t, nbr, s); break;
+    case 5: bt_neighbors_launch<5, 16>(indices, n, t, nbr, s); break;
+    default: bt_neighbors_launch<7, 4>(indices, n, t, nbr, s); break;
   }
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;

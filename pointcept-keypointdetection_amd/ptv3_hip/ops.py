@@ -320,6 +320,20 @@ def subm_neighbors(indices, ksize, table=None):
     return nbr, table
 
 
+def subm_neighbors_blocks(indices, ksize, table=None):
+    """subm_neighbors() through the table of 4x4x4 blocks (ptv3_subm_build_block_table): the same nbr, bitwise."""
+    _chk(indices, "indices", torch.int32, 2)
+    n = indices.shape[0]
+    if table is None:
+        table = torch.empty(lib.ptv3_subm_block_table_bytes(n), dtype=torch.uint8, device=indices.device)
+        lib.check(lib.ptv3_subm_build_block_table(_p(indices), n, _p(table), table.numel(), _stream()),
+                  "ptv3_subm_build_block_table")
+    nbr = torch.empty((n, ksize ** 3), dtype=torch.int32, device=indices.device)
+    lib.check(lib.ptv3_subm_neighbors_blocks(_p(indices), n, _p(table), table.numel(), int(ksize), _p(nbr), _stream()),
+              "ptv3_subm_neighbors_blocks")
+    return nbr, table
+
+
 def gemm(x, w, bias=None, nbr=None, kvol=1, row_order=None, bn_scale=None, bn_shift=None, act=ACT_NONE,
          res=None, res_index=None, dual=False, m=None):
     """out = epi(sum_d sum_c w[o][d][c] x[nbr[i][d]][c]); see ptv3_gemm in include/ptv3_hip.h.
