@@ -81,12 +81,17 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(AttnBwdArgs a) {
   const int64_t pq = slot0 + (qv ? jq : P - 1);
   const int64_t src = a.win_order[pq];
   const bool kept = qv && a.win_inverse[src] == pq;
-  // stationary fragments: Q^T and dO^T as B operands (lane (i, g): dims 16nd+4g..+3 of query i)
+  // stationary fragments: Q^T and dO^T as B operands (lane (i, g): dims 16nd+4g..+3 of query i).  Q is pre-scaled by
+  // scale * log2(e) and packed to T exactly as the forward kernels do it (window_attn.hip), so the scores recomputed
+  // here are the forward's scores: in bf16 the rounding of the scaled q moves a score of 2^7 by up to half a log2
+  // unit, and probabilities taken against the forward's lse would no longer sum to one
   V4 qf[ND], dof[ND];
   float dpart = 0.f;
 #pragma unroll
   for (int nd = 0; nd < ND; ++nd) {
-    qf[nd] = *reinterpret_cast<const V4*>(qkv + src * c3 + h * D + 16 * nd + 4 * g);
+    float qraw[4];
+    unpack4<T>(*reinterpret_cast<const V4*>(qkv + src * c3 + h * D + 16 * nd + 4 * g), qraw);
+    qf[nd] = pack4<T>(qraw[0] * a.scale_log2e, qraw[1] * a.scale_log2e, qraw[2] * a.scale_log2e, qraw[3] * a.scale_log2e);
     dof[nd] = zero4<T>();
     if (kept) {
       dof[nd] = *reinterpret_cast<const V4*>(reinterpret_cast<const T*>(a.dout) + src * a.c + h * D + 16 * nd + 4 * g);
@@ -140,7 +145,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(AttnBwdArgs a) {
 #pragma unroll
     for (int nd = 0; nd < ND; ++nd)
       s = mma16<T>(*reinterpret_cast<const V4*>(sK + (16 * kt + i) * D + 16 * nd + 4 * g), qf[nd], s);
-    return s;  // s[r] = q_i . k_(16kt+4g+r)
+    return s;  // s[r] = scale * log2(e) * q_i . k_(16kt+4g+r)
   };
 
   // ---- sweep 1: log-sum-exp of the scaled scores (log2 domain) - unless the training forward left it
@@ -155,7 +160,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(AttnBwdArgs a) {
       float t[4], mx = -INFINITY;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        t[r] = kc0 + 16 * kt + 4 * g + r < P ? s[r] * a.scale_log2e : -INFINITY;
+        t[r] = kc0 + 16 * kt + 4 * g + r < P ? s[r] : -INFINITY;
         if constexpr (RPE) t[r] += rpe_pair_bias(sTab, qg, sG + 3 * (16 * kt + 4 * g + r), a.pos_bnd, rpe_num);
         mx = fmaxf(mx, t[r]);
       }
@@ -194,7 +199,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(AttnBwdArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const bool kin = kc0 + 16 * kt + 4 * g + r < P;
-        float sc = s[r] * a.scale_log2e;
+        float sc = s[r];
         const int* kg = sG + (RPE ? 3 * (16 * kt + 4 * g + r) : 0);
         if constexpr (RPE) sc += rpe_pair_bias(sTab, qg, kg, a.pos_bnd, rpe_num);
         const float p = kin ? __builtin_amdgcn_exp2f(sc - lse2) : 0.f;
@@ -299,7 +304,10 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnBwdArgs a) {
         if (a.win_inverse[qs] == p)
           ov4 = *reinterpret_cast<const V4*>(reinterpret_cast<const T*>(a.dout) + qs * a.c + h * D + 4 * dv);
       }
-      *reinterpret_cast<V4*>(sQ + q * D + 4 * dv) = qv4;
+      float qraw[4];   // score operand: scaled and packed as in the forward and in pass A; dK takes the raw rows (sQt)
+      unpack4<T>(qv4, qraw);
+      *reinterpret_cast<V4*>(sQ + q * D + 4 * dv) =
+          pack4<T>(qraw[0] * a.scale_log2e, qraw[1] * a.scale_log2e, qraw[2] * a.scale_log2e, qraw[3] * a.scale_log2e);
       *reinterpret_cast<V4*>(sO + q * D + 4 * dv) = ov4;
       const T* qe = reinterpret_cast<const T*>(&qv4);
       const T* oe = reinterpret_cast<const T*>(&ov4);
@@ -332,7 +340,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(AttnBwdArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int q = 16 * qt + 4 * g + r;
-        float sc = s[r] * a.scale_log2e;
+        float sc = s[r];
         if constexpr (RPE) sc += rpe_pair_bias(sTab, sG + 3 * q, kg, a.pos_bnd, rpe_num);
         p[r] = __builtin_amdgcn_exp2f(sc - sL[q]);
         float dpe = dp[r];

@@ -634,6 +634,7 @@ static int launch_window_attn(const void* qkv, const int32_t* wo, const int32_t*
   constexpr int QB = WA_WAVES * QT * 16;
   const int qsplit = (K + QB - 1) / QB;
   const size_t lds = (size_t)(WA_KT * (D + 4) + D * (WA_KT + 4)) * sizeof(T) + (size_t)K * 4;
+  if (lds > 64 * 1024) ensure_dynamic_lds(reinterpret_cast<const void*>(&window_attn_kernel<T, ND>), 160 * 1024);
   const unsigned nwg = (unsigned)nwin * H * qsplit;
   hipLaunchKernelGGL((window_attn_kernel<T, ND>), dim3(nwg), dim3(WA_THREADS), lds, s, (const T*)qkv, wo, wi,
                      (T*)out, C, H, K, nwin, qsplit, scale * 1.44269504088896340736f, rpe, cu, 0u, 0u, 1.f, lse);
