@@ -231,6 +231,29 @@ int ptv3_subm_conv_ln(const void* x, const void* w, const int32_t* nbr, const in
                       const float* gamma, const float* beta, void* out, int64_t m, int c, int kvol, float eps, int act,
                       int dtype, void* stream);
 
+/* ---- residual-block convolution of SpUNet (pointcept/models/sparse_unet/spconv_unet_v1m1_base.py:72-85, BasicBlock.forward,
+ * and :269-273, the decoder's cat(up, skip); csrc/res_conv.hip) ---------------------------------------------------
+ * One launch, fp32 (exact-fp32 matrix-core steps):
+ *   x[i]       = concat(xa[i] (ca channels), xb[i] (cb channels))          cb = 0, xb = NULL: one source
+ *   y[i][o]    = sum_{d<kvol} sum_{c<ca+cb} w[o][d][c] * x[nbr[i][d]][c]   nbr -1 = inactive, as ptv3_gemm
+ *   out[i][o]  = act(y * bn_scale[o] + bn_shift[o] + res[i][o])            res optional: the residual BEFORE act
+ *   proj[i][o] = (sum_c w_proj[o][c] * x[i][c]) * proj_scale[o] + proj_shift[o]     optional second output, no act
+ * w (cout, kvol, ca+cb), w_proj (cout, ca+cb), kvol = 27; nbr (m, 27) and row_order (m) as in ptv3_gemm; xa (m, ca),
+ * xb (m, cb), res / out / proj_out (m, cout).  The concatenation is never written and the projection reuses the centre
+ * tap's rows of the conv's own operand tile (a non-finite x[nbr[i][d]] of the taps that share a K step with the centre
+ * tap reaches proj[i] as NaN).  A table or row_order entry outside [0, m) counts as absent.
+ * ca, cb, cout multiples of 4, ca >= 4, ca + cb <= 1024, cout <= 512 (ptv3_res_conv_capable; m only has to be in
+ * [1, 2^31)): anything else is refused before any launch, PTV3_ERR_ARG for a malformed call, PTV3_ERR_UNSUPPORTED for
+ * a well-formed shape outside the served range.  No allocation, no synchronisation. */
+int ptv3_res_conv_capable(int64_t m, int ca, int cb, int cout, int kvol);
+/* 16-point row tiles per wave the launch takes for (m, cout): 1 (64-point workgroups) or 2 (128-point workgroups,
+ * chosen once they still give every CU two workgroups); 0 for a cout outside [4, 512] or m < 1.  For tests and tools. */
+int ptv3_res_conv_row_tiles(int64_t m, int cout);
+int ptv3_res_conv(const float* xa, const float* xb, const float* w, const int32_t* nbr, const int32_t* row_order,
+                  const float* bn_scale, const float* bn_shift, const float* res, int act, float* out,
+                  const float* w_proj, const float* proj_scale, const float* proj_shift, float* proj_out, int64_t m,
+                  int ca, int cb, int cout, int kvol, void* stream);
+
 /* ---- normalisation / elementwise -------------------------------------------------------------
  * torch.nn.LayerNorm over the last dim (Block.cpe[2], norm1, norm2; :277-304): y = LN(x)*g+b [+ res];
  * optional second output y2 = LN2(y) * g2 + b2 (fuses `shortcut + cpe` with the following norm1). */

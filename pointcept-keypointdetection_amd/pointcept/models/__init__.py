@@ -19,3 +19,5 @@ from .keypoint_oa_cnns import KeypointOACNNs  # noqa: F401
 from .point_transformer_v2 import PointTransformerV2  # noqa: F401
 from .keypoint_ptv2 import KeypointPTv2  # noqa: F401
 from .keypoint_ptv3_plus import BlockPlus, PointTransformerV3Plus, KeypointPTv3Plus  # noqa: F401
+from .sparse_unet import SpUNetBase  # noqa: F401
+from .keypoint_sparse_unet import KeypointSparseUNet  # noqa: F401

@@ -81,6 +81,11 @@ KEYPOINT_OACNNS_CFG = dict(
     point_grid_size=[[8, 12, 16, 16], [6, 9, 12, 12], [4, 6, 8, 8], [3, 4, 6, 6]], dec_depth=[2, 2, 2, 2],
     enc_num_ref=[16, 16, 16, 16], hidden_dim=256,
 )
+# the fork's SpUNet regression model (configs/my_dataset/keypoint_sparse_unet.py:16-34), run at batch size 8
+KEYPOINT_SPUNET_CFG = dict(
+    type="KeypointSparseUNet", num_keypoints=6, in_channels=4, num_classes=0, base_channels=32,
+    channels=(32, 64, 128, 256, 256, 128, 96, 96), layers=(2, 3, 4, 6, 2, 2, 2, 2), enc_mode=False, hidden_dim=256,
+)
 
 # the fork's Point Transformer V2 regression model (configs/my_dataset/keypoint_ptv2.py:11-54), run at batch size 8
 KEYPOINT_PTV2_CFG = dict(

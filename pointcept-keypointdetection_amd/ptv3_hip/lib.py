@@ -69,6 +69,9 @@ SIGNATURES = {
     "ptv3_rows_linear_ln": (c_int, [P, P, P, P, P, P, c_int64, c_int, c_int, c_float, c_int, c_int, P]),
     "ptv3_subm_conv_ln_capable": (c_int, [c_int, c_int, c_int]),
     "ptv3_subm_conv_ln": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int, c_int, c_float, c_int, c_int, P]),
+    "ptv3_res_conv_capable": (c_int, [c_int64, c_int, c_int, c_int, c_int]),
+    "ptv3_res_conv_row_tiles": (c_int, [c_int64, c_int]),
+    "ptv3_res_conv": (c_int, [P, P, P, P, P, P, P, P, c_int, P, P, P, P, P, c_int64, c_int, c_int, c_int, c_int, P]),
     "ptv3_mlp2_fusable": (c_int, [c_int, c_int, c_int, c_int]),
     "ptv3_mlp2": (c_int, [P, P, P, P, P, c_int, P, P, P, c_int, c_int64, c_int, c_int, c_int, c_int, P]),
     "ptv3_layernorm": (c_int, [P, P, P, P, P, P, P, P, c_int64, c_int, c_float, c_int, P]),

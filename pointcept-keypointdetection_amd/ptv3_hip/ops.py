@@ -376,6 +376,11 @@ def gemm(x, w, bias=None, nbr=None, kvol=1, row_order=None, bn_scale=None, bn_sh
     return (out, out2) if dual else out
 
 
+def gemm_splits(m, cin, cout, kvol, dtype):
+    """K slabs ptv3_gemm splits the shape into (1: a single pass)."""
+    return int(lib.ptv3_gemm_splits(int(m), int(cin), int(cout), int(kvol), _DT[dtype]))
+
+
 def block_fusable(c, hidden, dtype, m=0):
     """0: no fused block kernels; 1: wave-local register chain (chain_permute'd weights); 2: workgroup-cooperative
     (natural weights)."""
@@ -1548,6 +1553,57 @@ def add_act(a, b, act=ACT_NONE):
     out = torch.empty_like(a)
     lib.check(lib.ptv3_add_act(_p(a), _p(b), int(act), _p(out), a.numel(), _stream()), "ptv3_add_act")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# SpUNet: the residual-block convolution (fp32)
+# ---------------------------------------------------------------------------------------------
+def res_conv_capable(m, ca, cb, cout, kvol=27):
+    """Whether ptv3_res_conv serves the shape (include/ptv3_hip.h); `ops.res_conv` refuses the others."""
+    return bool(lib.ptv3_res_conv_capable(int(m), int(ca), int(cb), int(cout), int(kvol)))
+
+
+def res_conv_row_tiles(m, cout):
+    """16-point row tiles per wave ptv3_res_conv takes at (m, cout): 1 or 2 (which kernel instantiations a shape runs)."""
+    return int(lib.ptv3_res_conv_row_tiles(int(m), int(cout)))
+
+
+def res_conv(xa, w, nbr, xb=None, bn_scale=None, bn_shift=None, res=None, act=ACT_NONE, w_proj=None, proj_scale=None,
+             proj_shift=None, row_order=None):
+    """out = act(conv3x3x3(cat(xa, xb)) * bn_scale + bn_shift + res), and with w_proj also
+    proj = (cat(xa, xb) @ w_proj^T) * proj_scale + proj_shift, in one launch; see ptv3_res_conv in include/ptv3_hip.h.
+
+    Returns out, or (out, proj) when w_proj is given."""
+    _chk(xa, "xa", torch.float32, 2)
+    _chk(xb, "xb", torch.float32, 2)
+    _chk(w, "w", torch.float32)
+    _chk(w_proj, "w_proj", torch.float32)
+    _chk(nbr, "nbr", torch.int32, 2)
+    _chk(row_order, "row_order", torch.int32, 1)
+    _chk(res, "res", torch.float32, 2)
+    m, ca = xa.shape
+    cb = 0 if xb is None else xb.shape[1]
+    cout, kvol = w.shape[0], nbr.shape[1]
+    if nbr.shape[0] != m or (xb is not None and xb.shape[0] != m):
+        raise RuntimeError("res_conv: xa, xb and nbr must have one row per site")
+    if w.numel() != cout * kvol * (ca + cb):
+        raise RuntimeError(f"res_conv: weight has {w.numel()} elements, expected {cout}x{kvol}x{ca + cb}")
+    if w_proj is not None and w_proj.numel() != cout * (ca + cb):
+        raise RuntimeError(f"res_conv: w_proj has {w_proj.numel()} elements, expected {cout}x{ca + cb}")
+    if w_proj is None and proj_scale is not None:
+        raise RuntimeError("res_conv: proj_scale without w_proj")
+    _epi(bn_scale, bn_shift, cout)
+    _epi(proj_scale, proj_shift, cout)
+    if res is not None and tuple(res.shape) != (m, cout):
+        raise RuntimeError("res_conv: residual shape mismatch")
+    if row_order is not None and row_order.shape[0] != m:
+        raise RuntimeError("res_conv: row_order length != m")
+    out = torch.empty((m, cout), dtype=torch.float32, device=xa.device)
+    proj = torch.empty_like(out) if w_proj is not None else None
+    lib.check(lib.ptv3_res_conv(_p(xa), _p(xb), _p(w), _p(nbr), _p(row_order), _p(bn_scale), _p(bn_shift), _p(res),
+                                int(act), _p(out), _p(w_proj), _p(proj_scale), _p(proj_shift), _p(proj), m, ca, cb, cout,
+                                kvol, _stream()), "ptv3_res_conv")
+    return out if proj is None else (out, proj)
 
 
 # ---------------------------------------------------------------------------------------------
