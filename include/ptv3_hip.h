@@ -859,6 +859,66 @@ int ptv3_grid_keys(const float* coord, int64_t n, const int64_t* offset, int num
 int ptv3_segment_mean3(const float* coord, const int64_t* order, const int32_t* seg_start, int64_t n_out, float* out,
                        void* stream);
 
+/* ---- Stratified Transformer (ST-v1m2) window attention, eval forward (fp32) -----------------------------
+ * The reference (pointcept/models/stratified_transformer/stratified_transformer_v1m2_refine.py) builds [windows, k, k]
+ * masks and an edge list of M (query, key) pairs per block (BasicLayer.forward, :388-450) and attends over it with
+ * pointops2's attention_step1_v2 / dot_prod_with_idx_v3 / attention_step2_with_rel_pos_value_v2 and a scatter_softmax
+ * (WindowAttention.forward, :157-216; libs/pointops2/src/attention_v2, rpe_v2).  Every query of one (small window,
+ * large window) pair has the same keys, so the plan here is a list of GROUPS and nothing per edge exists:
+ *   q_ptr (G+1) / q_rows (n):  the rows of each group - every point is a query of exactly one group; a group is the
+ *                              set of points that share a small window AND a large window
+ *   k_ptr (G+1) / k_rows:      its keys - all rows of its small window, then the sampled rows of its large window that
+ *                              lie in another small window.
+ * ptv3_strat_cell_keys replaces the four grid_sample calls (:373-385): small cell = trunc(((x + s) - min) / w), large
+ * cell = trunc(((x + 2 s) - min) / 2w), s = w / 2 in shifted blocks and 0 otherwise, each evaluated in fp32 operation by
+ * operation as voxel_grid does and NEVER derived from the other (in shifted blocks a small window straddles two large
+ * ones); coord_min (3) on the device is the batch-wide minimum (:372).  Two keys per point:
+ *   key_small = scene << 51 | small cell (9 bits per axis) << 24 | large cell (8 bits per axis)
+ *   key_large = scene << 51 | large cell << 27 | small cell
+ * *bad (device, zeroed by the caller) is set when a cell does not fit.  ptv3_argsort_i64(key, end_bit 63) of each and
+ * ptv3_pool_segments then give: from key_small, shift 0: q_rows = order_s and q_ptr; shift 24: the small windows' runs
+ * c_ptr with cell_of (n); from key_large, shift 0: the same groups' runs lg_ptr in order_l with lgroup_of (n); shift 27:
+ * the large windows' runs w_ptr with window_of (n).
+ * ONE DELIBERATE DIFFERENCE: in shifted blocks the reference excludes sparse keys by trunc((x - min + w/2) / w) (:423),
+ * which associates differently from voxel_grid's ((x + w/2) - min) / w; a point within rounding of a cell face can then be
+ * a key twice.  Here the voxel_grid expression serves both uses.
+ * ptv3_strat_key_count: count[g] for g < *n_groups (device), 0 for the other g < n.  sampled (n) uint8 marks down_idx;
+ * sampled_prefix (n+1) int32 = exclusive prefix sum of sampled[order_l[.]].  The caller scans count into k_ptr, reads the
+ * totals once, and ptv3_strat_key_fill writes s_rows (number of sampled rows) and k_rows. */
+int ptv3_strat_cell_keys(const float* coord, int64_t n, const int32_t* offset, int num_scenes, const float* coord_min,
+                         float window, int shifted, int64_t* key_small, int64_t* key_large, int32_t* bad, void* stream);
+int ptv3_strat_key_count(const int32_t* q_ptr, const int64_t* order_s, const int64_t* cell_of, const int32_t* c_ptr,
+                         const int64_t* lgroup_of, const int32_t* lg_ptr, const int64_t* window_of, const int32_t* w_ptr,
+                         const int32_t* sampled_prefix, const int32_t* n_groups, int64_t n, int32_t* count, void* stream);
+int ptv3_strat_key_fill(const int32_t* q_ptr, const int64_t* order_s, const int64_t* cell_of, const int32_t* c_ptr,
+                        const int64_t* lgroup_of, const int32_t* lg_ptr, const int64_t* window_of, const int32_t* w_ptr,
+                        const int64_t* order_l, const uint8_t* sampled, const int32_t* sampled_prefix, int64_t n,
+                        int64_t n_groups, const int32_t* k_ptr, int32_t* s_rows, int32_t* k_rows, void* stream);
+/* relative_position_index (:163-169) of m pairs: out (m,3) int32 =
+ *   trunc((round((x_i - x_j) * 1e5) / 1e5 + 2 window - 1e-4) / quant), clamped to [0, table_rows),
+ * bit for bit what torch's CPU kernels give in fp32 (one rounding per operation, IEEE division, round-half-even); the
+ * same device function serves ptv3_strat_attn_fwd.  Used by the edge composition and by tests. */
+int ptv3_strat_rel_index(const float* coord, const int32_t* qi, const int32_t* kj, int64_t m, float window, float quant,
+                         int table_rows, int32_t* out, void* stream);
+/* One launch for WindowAttention.forward between qkv and proj (:157-220), with qs = scale * q:
+ *   e_ij  = qs_i . k_j + sum_a ( qs_i . Tq[r_a,h,:,a] + k_j . Tk[r_a,h,:,a] )
+ *   out_i = sum_j softmax_j(e_ij) ( v_j + sum_a Tv[r_a,h,:,a] )        over the keys j of i's group
+ * q, k, v: rows of `ld` floats (views into the qkv projection), head h at [16 h, 16 h + 16); coord (n,3); tq / tk / tv:
+ * the (2L, heads, 16, 3) tables repacked axis-major to (3, table_rows, heads, 16); out (n, heads, 16), written for the
+ * plan's query rows only.  head_dim 16 and 1 <= table_rows <= 80 (ptv3_strat_attn_capable), anything else is refused
+ * with PTV3_ERR_ARG before a launch.  One wave per (group, head); keys stream through in chunks of 16 with a running
+ * maximum and sum; all products on v_mfma_f32_16x16x4_f32; fp32, no atomics, bitwise reproducible. */
+int ptv3_strat_attn_capable(int heads, int head_dim, int table_rows);
+int ptv3_strat_attn_fwd(const float* q, const float* k, const float* v, int64_t ld, const float* coord, const float* tq,
+                        const float* tk, const float* tv, const int32_t* q_ptr, const int32_t* q_rows,
+                        const int32_t* k_ptr, const int32_t* k_rows, int64_t n_groups, int heads, int head_dim,
+                        int table_rows, float scale, float window, float quant, float* out, void* stream);
+/* torch_points_kernels.ball_query(radius, max_neighbor, x, x, mode="partial_dense", batch_x, batch_x)[0] as the model
+ * calls it (:703-711; the package is not in the reference tree: PARITY UNPINNED).  idx (n, max_neighbor) int64: the first
+ * max_neighbor rows j of i's own scene, in index order, with |x_i - x_j|^2 < radius^2 (i itself included), then -1. */
+int ptv3_ball_query(const float* xyz, const int32_t* offset, int num_scenes, int64_t n, float radius, int max_neighbor,
+                    int64_t* idx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

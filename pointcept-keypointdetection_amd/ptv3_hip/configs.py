@@ -99,6 +99,16 @@ KEYPOINT_PTV2_CFG = dict(
         drop_path_rate=0.3, enable_checkpoint=False, unpool_backend="map"),
 )
 
+# the fork's Stratified Transformer regression model (configs/my_dataset/keypoint_stratified_transformer.py:12-45), run at
+# batch size 8
+KEYPOINT_STRAT_CFG = dict(
+    type="KeypointStratifiedTransformer", num_keypoints=6, in_channels=4, channels=[48, 96, 192, 384, 384],
+    num_heads=[6, 12, 24, 24], depths=[3, 9, 3, 3], window_size=[0.2, 0.4, 0.8, 1.6],
+    quant_size=[0.01, 0.02, 0.04, 0.08], mlp_expend_ratio=4.0, down_ratio=0.25, down_num_sample=16, kp_ball_radius=0.05,
+    kp_max_neighbor=34, kp_grid_size=0.02, kp_sigma=1.0, drop_path_rate=0.2, rel_query=True, rel_key=True,
+    rel_value=True, qkv_bias=True, stem=True, hidden_dim=256,
+)
+
 # plumbing-size Swin3D: three levels, both head widths the kernel is built for (8 and 16)
 TINY_SWIN3D_CFG = dict(
     type="Swin3D-v1m1", in_channels=9, num_classes=13, base_grid_size=0.02, depths=[2, 2, 2], channels=[16, 32, 32],

@@ -168,6 +168,14 @@ SIGNATURES = {
     "ptv3_gva_fwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P, P, P]),
     "ptv3_grid_keys": (c_int, [P, c_int64, P, c_int, c_float, P, P, P, P, P]),
     "ptv3_segment_mean3": (c_int, [P, P, P, c_int64, P, P]),
+    "ptv3_strat_cell_keys": (c_int, [P, c_int64, P, c_int, P, c_float, c_int, P, P, P, P]),
+    "ptv3_strat_key_count": (c_int, [P, P, P, P, P, P, P, P, P, P, c_int64, P, P]),
+    "ptv3_strat_key_fill": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, P, P, P, P]),
+    "ptv3_strat_rel_index": (c_int, [P, P, P, c_int64, c_float, c_float, c_int, P, P]),
+    "ptv3_strat_attn_capable": (c_int, [c_int, c_int, c_int]),
+    "ptv3_strat_attn_fwd": (c_int, [P, P, P, c_int64, P, P, P, P, P, P, P, P, c_int64, c_int, c_int, c_int, c_float,
+                                    c_float, c_float, P, P]),
+    "ptv3_ball_query": (c_int, [P, P, c_int, c_int64, c_float, c_int, P, P]),
 }
 
 

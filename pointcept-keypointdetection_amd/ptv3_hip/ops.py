@@ -1688,3 +1688,189 @@ def segment_mean3(coord, order, seg_start, n_out):
     lib.check(lib.ptv3_segment_mean3(_p(coord), _p(order), _p(seg_start), n_out, _p(out), _stream()),
               "ptv3_segment_mean3")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# Stratified Transformer (ST-v1m2)
+# ---------------------------------------------------------------------------------------------
+class StratPlan:
+    """The attention plan of one BasicLayer parity: group g has the query rows q_rows[q_ptr[g]:q_ptr[g+1]] (every point
+    in exactly one group) and the key rows k_rows[k_ptr[g]:k_ptr[g+1]] (ptv3_strat_cell_keys in include/ptv3_hip.h);
+    all four int32 on the device, n_groups and n_keys (= number of (query group, key) slots) on the host."""
+
+    def __init__(self, q_ptr, q_rows, k_ptr, k_rows, n_groups, n_keys, n_windows):
+        self.q_ptr, self.q_rows, self.k_ptr, self.k_rows = q_ptr, q_rows, k_ptr, k_rows
+        self.n_groups, self.n_keys, self.n_windows = n_groups, n_keys, n_windows
+
+    def edges(self):
+        """(index_0, index_1) int64, sorted by query row as BasicLayer.forward leaves them (:441-442): the edge list the
+        reference attends over, expanded on the device for the composition and the training path."""
+        q_ptr, k_ptr = self.q_ptr.long(), self.k_ptr.long()
+        nq, nk = q_ptr[1:] - q_ptr[:-1], k_ptr[1:] - k_ptr[:-1]
+        n = self.q_rows.shape[0]
+        grp = torch.repeat_interleave(torch.arange(self.n_groups, device=q_ptr.device), nq, output_size=n)
+        per_q = nk[grp]                                        # keys of every query, in q_rows order
+        m = int(per_q.sum().item())
+        qpos = torch.repeat_interleave(torch.arange(n, device=q_ptr.device), per_q, output_size=m)
+        first = torch.cumsum(per_q, 0) - per_q
+        slot = torch.arange(m, device=q_ptr.device) - first[qpos]
+        index_0 = self.q_rows.long()[qpos]
+        index_1 = self.k_rows.long()[k_ptr[grp[qpos]] + slot]
+        index_0, perm = torch.sort(index_0, stable=True)
+        return index_0, index_1[perm]
+
+
+def stratified_plan(coord, offset, down_idx, window, shifted, coord_min=None):
+    """StratPlan of coord (n, 3) fp32 with int32 cumulative scene ends `offset` (b) on the device, for window size
+    `window` and the sampled rows down_idx (int32 / int64).  ptv3_strat_cell_keys + ptv3_argsort_i64 + four
+    ptv3_pool_segments + ptv3_strat_key_count / _fill; the scans between them are torch.cumsum.  One host read: number of
+    groups, of large windows, of key slots, and the flag of a cell outside the key."""
+    _chk(coord, "coord", torch.float32, 2)
+    _chk(offset, "offset", torch.int32, 1)
+    _chk(down_idx, "down_idx", (torch.int32, torch.int64), 1)
+    n, b, dev = coord.shape[0], offset.shape[0], coord.device
+    if coord.shape[1] != 3 or n < 1:
+        raise RuntimeError("stratified_plan: coord must be (n, 3) with n >= 1")
+    cmin = (coord.min(0).values if coord_min is None else coord_min).contiguous()
+    keys = torch.empty((2, n), dtype=torch.int64, device=dev)     # [key_small, key_large]
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    lib.check(lib.ptv3_strat_cell_keys(_p(coord), n, _p(offset), b, _p(cmin), float(window), int(bool(shifted)),
+                                       keys[0].data_ptr(), keys[1].data_ptr(), _p(bad), _stream()),
+              "ptv3_strat_cell_keys")
+    orders = argsort_codes(keys, 63)[0]
+    order_s, order_l = orders[0], orders[1]
+    ws_bytes = lib.ptv3_pool_workspace_bytes(n)
+    ws = _ws(ws_bytes, dev)
+
+    def segments(which, shift):
+        cluster = torch.empty(n, dtype=torch.int64, device=dev)
+        seg_start = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        n_out = torch.empty(1, dtype=torch.int32, device=dev)
+        lib.check(lib.ptv3_pool_segments(keys[which].data_ptr(), orders[which].data_ptr(), n, shift, None, _p(cluster),
+                                         _p(seg_start), _p(n_out), None, _p(ws), ws_bytes, _stream()),
+                  "ptv3_pool_segments")
+        return cluster, seg_start, n_out
+
+    _, q_ptr, n_groups = segments(0, 0)
+    cell_of, c_ptr, _ = segments(0, 24)
+    lgroup_of, lg_ptr, _ = segments(1, 0)
+    window_of, w_ptr, n_windows = segments(1, 27)
+    sampled = torch.zeros(n, dtype=torch.uint8, device=dev)
+    sampled[down_idx.long()] = 1
+    prefix = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+    torch.cumsum(sampled[order_l], 0, dtype=torch.int32, out=prefix[1:])
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    where = (_p(q_ptr), _p(order_s), _p(cell_of), _p(c_ptr), _p(lgroup_of), _p(lg_ptr), _p(window_of), _p(w_ptr))
+    lib.check(lib.ptv3_strat_key_count(*where, _p(prefix), _p(n_groups), n, _p(count), _stream()),
+              "ptv3_strat_key_count")
+    k_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(count, 0, out=k_ptr[1:])
+    g, nw, total, flag = torch.cat([n_groups.long(), n_windows.long(), k_ptr[-1:], bad.long()]).tolist()   # the one read
+    if flag:
+        raise ValueError(f"stratified_plan: the batch spans more than 512 windows of size {window} along an axis")
+    if total >= 1 << 31:
+        raise ValueError(f"stratified_plan: {total} key slots do not fit int32")
+    k_ptr = k_ptr[:g + 1].int()
+    q_ptr = q_ptr[:g + 1]
+    s_rows = torch.empty(max(int(down_idx.shape[0]), 1), dtype=torch.int32, device=dev)
+    k_rows = torch.empty(total, dtype=torch.int32, device=dev)
+    lib.check(lib.ptv3_strat_key_fill(*where, _p(order_l), _p(sampled), _p(prefix), n, g, _p(k_ptr), _p(s_rows),
+                                      _p(k_rows), _stream()), "ptv3_strat_key_fill")
+    return StratPlan(q_ptr, order_s.int(), k_ptr, k_rows, g, total, nw)
+
+
+def strat_attn_capable(heads, head_dim, table_rows):
+    return bool(lib.ptv3_strat_attn_capable(int(heads), int(head_dim), int(table_rows)))
+
+
+def strat_pack_tables(table):
+    """(2L, heads, head_dim, 3) relative-position table -> (3, 2L, heads, head_dim) fp32 axis-major slabs; once per
+    load_state_dict / parameter update (callers cache it on the parameter's version)."""
+    return table.detach().float().permute(3, 0, 1, 2).contiguous()
+
+
+def strat_rel_index(coord, index_0, index_1, window, quant, table_rows):
+    """(m, 3) int32: relative_position_index of the pairs (index_0[e], index_1[e]), exactly torch's CPU fp32 values
+    (ptv3_strat_rel_index)."""
+    _chk(coord, "coord", torch.float32, 2)
+    i0, i1 = index_0.int().contiguous(), index_1.int().contiguous()
+    _chk(i0, "index_0", torch.int32, 1)
+    _chk(i1, "index_1", torch.int32, 1)
+    if i0.shape != i1.shape or coord.shape[1] != 3:
+        raise RuntimeError("strat_rel_index: index_0 / index_1 (m) and coord (n, 3) expected")
+    out = torch.empty((i0.shape[0], 3), dtype=torch.int32, device=coord.device)
+    lib.check(lib.ptv3_strat_rel_index(_p(coord), _p(i0), _p(i1), i0.shape[0], float(window), float(quant),
+                                       int(table_rows), _p(out), _stream()), "ptv3_strat_rel_index")
+    return out
+
+
+def _check_strat_plan(plan, n):
+    """Host check of a plan's ranges (tests and hand-made plans; plans of stratified_plan come from the kernels)."""
+    q_ptr, k_ptr = plan.q_ptr.tolist(), plan.k_ptr.tolist()
+    g = plan.n_groups
+    ok = len(q_ptr) == g + 1 and len(k_ptr) == g + 1 and q_ptr[0] == 0 and k_ptr[0] == 0 and \
+        all(a <= b for a, b in zip(q_ptr, q_ptr[1:])) and all(a <= b for a, b in zip(k_ptr, k_ptr[1:])) and \
+        q_ptr[-1] <= plan.q_rows.shape[0] and k_ptr[-1] <= plan.k_rows.shape[0]
+    for rows in (plan.q_rows, plan.k_rows):
+        if rows.numel():
+            lo, hi = rows.min().item(), rows.max().item()
+            ok = ok and lo >= 0 and hi < n
+    if not ok:
+        raise ValueError("stratified_attention: the plan's pointers or rows are out of range")
+
+
+def stratified_attention(qkv, coord, plan, tq, tk, tv, scale, window, quant, out=None, check=False):
+    """out (n, heads, head_dim) fp32 = WindowAttention.forward between qkv and proj over the groups of `plan`
+    (ptv3_strat_attn_fwd).  qkv (n, 3, heads, head_dim) fp32, the projection's output; tq / tk / tv from
+    strat_pack_tables.  Rows that are no query of the plan keep what `out` held (zeros when it is allocated here)."""
+    _chk(qkv, "qkv", torch.float32, 4)
+    _chk(coord, "coord", torch.float32, 2)
+    n, three, heads, hd = qkv.shape
+    rows = tq.shape[1]
+    for t, nm in ((tq, "tq"), (tk, "tk"), (tv, "tv")):
+        _chk(t, nm, torch.float32, 4)
+        if tuple(t.shape) != (3, rows, heads, hd):
+            raise RuntimeError(f"stratified_attention: {nm} has shape {tuple(t.shape)}, expected {(3, rows, heads, hd)}")
+    if three != 3 or tuple(coord.shape) != (n, 3):
+        raise RuntimeError("stratified_attention: qkv (n, 3, heads, head_dim) and coord (n, 3) expected")
+    if not strat_attn_capable(heads, hd, rows):
+        raise NotImplementedError(f"stratified_attention: heads={heads}, head_dim={hd}, table_rows={rows} is not served "
+                                  "by ptv3_strat_attn_fwd (head_dim 16, at most 80 table rows)")
+    for t, nm in ((plan.q_ptr, "q_ptr"), (plan.q_rows, "q_rows"), (plan.k_ptr, "k_ptr"), (plan.k_rows, "k_rows")):
+        _chk(t, nm, torch.int32, 1)
+    if plan.q_ptr.shape[0] != plan.n_groups + 1 or plan.k_ptr.shape[0] != plan.n_groups + 1:
+        raise RuntimeError("stratified_attention: q_ptr / k_ptr must hold n_groups + 1 entries")
+    if check:
+        _check_strat_plan(plan, n)
+    if out is None:
+        out = torch.zeros((n, heads, hd), dtype=torch.float32, device=qkv.device)
+    else:
+        _chk(out, "out", torch.float32, 3)
+        if tuple(out.shape) != (n, heads, hd):
+            raise RuntimeError("stratified_attention: out must be (n, heads, head_dim)")
+    c = heads * hd
+    base = qkv.data_ptr()
+    lib.check(lib.ptv3_strat_attn_fwd(base, base + 4 * c, base + 8 * c, 3 * c, _p(coord), _p(tq), _p(tk), _p(tv),
+                                      _p(plan.q_ptr), _p(plan.q_rows), _p(plan.k_ptr), _p(plan.k_rows), plan.n_groups,
+                                      heads, hd, rows, float(scale), float(window), float(quant), _p(out), _stream()),
+              "ptv3_strat_attn_fwd")
+    return out
+
+
+def ball_query(radius, max_neighbor, xyz, offset, ends_host=None):
+    """idx (n, max_neighbor) int64: torch_points_kernels.ball_query(..., mode="partial_dense") of a cloud against
+    itself (ptv3_ball_query): per row the first max_neighbor rows of its scene within `radius`, in index order, then -1.
+    ends_host: the offsets as host integers when the caller has them (otherwise the last one is read back): the kernel
+    trusts the scene ends."""
+    _chk(xyz, "xyz", torch.float32, 2)
+    _chk(offset, "offset", torch.int32, 1)
+    n = xyz.shape[0]
+    if xyz.shape[1] != 3 or offset.shape[0] < 1:
+        raise RuntimeError("ball_query: xyz (n, 3) and at least one scene expected")
+    last = int(offset[-1].item()) if ends_host is None else ends_host[-1]
+    if last != n or (ends_host is not None and len(ends_host) != offset.shape[0]):
+        raise ValueError(f"ball_query: offsets end at {last} for {n} points")
+    idx = torch.empty((n, int(max_neighbor)), dtype=torch.int64, device=xyz.device)
+    lib.check(lib.ptv3_ball_query(_p(xyz), _p(offset), offset.shape[0], n, float(radius), int(max_neighbor), _p(idx),
+                                  _stream()), "ptv3_ball_query")
+    return idx
