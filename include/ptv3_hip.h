@@ -919,6 +919,41 @@ int ptv3_strat_attn_fwd(const float* q, const float* k, const float* v, int64_t 
 int ptv3_ball_query(const float* xyz, const int32_t* offset, int num_scenes, int64_t n, float radius, int max_neighbor,
                     int64_t* idx, void* stream);
 
+/* ---- OctFormer (pointcept/models/octformer/octformer_v1m1_base.py; ocnn and dwconv are not in the reference tree:
+ * PARITY UNPINNED) -------------------------------------------------------------------------------------------------
+ * Leaf keys of ocnn's Octree.build_octree (:598-604): p = coord / scale_factor, cell = floor((p + 1) * 2^(depth-1)) per
+ * axis in fp32 (one rounding per operation, IEEE division); key = scene << 48 | interleave(cell) with x in the highest
+ * bit of each triple, then y, then z.  coord (n,3) fp32; offset (num_scenes) int32 cumulative scene ends; depth in
+ * [1,16]; key (n) int64.  flag (1) int32, zeroed by the caller: set to 1 when some p lies outside -1 <= p < 1 (that
+ * point's cell is clamped into the grid; the caller reads the flag with the node counts and raises).  The nodes of depth
+ * d are then the runs of ptv3_argsort_i64(key, end_bit 63) + ptv3_pool_segments(key, order, 3*(depth-d)). */
+int ptv3_octree_keys(const float* coord, const int32_t* offset, int num_scenes, int64_t n, float scale_factor, int depth,
+                     int64_t* key, int32_t* flag, void* stream);
+/* OctreeAttention.forward between the qkv and proj linears (:230-257) in one launch, without the padded copy, the
+ * (patches, K, K) mask or the (patches, K, K, 3, H) table gather.  qkv (n_t, 3c) fp32 in node order, head h of q / k / v at
+ * columns [h hd, (h+1) hd) of its third; xyz (n_t, 3) int32 node coordinates; batch (n_t) int32 scene ids; rpe_table
+ * (3*(2*pos_bnd+1), heads) fp32; out (n_t, c) fp32 in node order.  Token j of patch d of group g is row
+ * g*patch*dilation + j*dilation + d; for a query i and a key j of one patch
+ *   logit_ij = (scale q_i) . k_j + sum_axis rpe_table[axis*(2b+1) + clamp(x_i - x_j, -b, b) + b][h],   b = pos_bnd,
+ * and out_i = sum_j softmax_j(logit_ij) v_j over the keys j of i's scene.  The reference adds -1e3 to the keys of other
+ * scenes and of the padding rows at or past n_t; exp of that is 0 in fp32 for logits of ordinary size, so the kernel
+ * SKIPS those keys.  Rows at or past n_t are neither read nor written.
+ * Covered (ptv3_octree_attn_capable): c / heads in {16, 32}, 1 <= patch <= 32, dilation >= 1; with pos_bnd <= 127.
+ * Anything else: PTV3_ERR_UNSUPPORTED (a shape the kernel does not cover) or PTV3_ERR_ARG (a malformed call) before any
+ * launch.  One wave per (patch, head), fp32 fused multiply-adds in a fixed order, 16-byte vector stores, no atomics:
+ * bitwise reproducible. */
+int ptv3_octree_attn_capable(int c, int heads, int patch, int dilation);
+int ptv3_octree_attn_fwd(const float* qkv, const int32_t* xyz, const int32_t* batch, const float* rpe_table, float* out,
+                         int64_t n_t, int c, int heads, int patch, int dilation, int pos_bnd, float scale, void* stream);
+/* cpe(data) + data of OctFormerBlock.forward in eval (:143-160, :310): dwconv.OctreeDWConv over the 27-tap table with the
+ * BatchNorm1d folded, plus the residual:
+ *   out[i][ch] = x[i][ch] + (sum_t w[t][ch] x[nbr[i][t]][ch]) * bn_scale[ch] + bn_shift[ch]
+ * x, out (n, c) fp32, out != x; w (27, c) fp32 (the (27, 1, c) parameter); nbr (n, 27) int32, tap (dx+1)*9 + (dy+1)*3 +
+ * (dz+1), an entry outside [0, n) is an absent tap; c % 4 == 0 (16-byte accesses), else PTV3_ERR_ARG.  Taps are summed in
+ * tap order: bitwise reproducible. */
+int ptv3_octree_dwconv(const float* x, const float* w, const int32_t* nbr, const float* bn_scale, const float* bn_shift,
+                       float* out, int64_t n, int c, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,3 +23,6 @@ from .sparse_unet import SpUNetBase  # noqa: F401
 from .keypoint_sparse_unet import KeypointSparseUNet  # noqa: F401
 from .stratified_transformer import StratifiedTransformer  # noqa: F401
 from .keypoint_stratified_transformer import KeypointStratifiedTransformer  # noqa: F401
+from .octformer import OctFormer  # noqa: F401
+from .keypoint_octformer import KeypointOctFormer  # noqa: F401
+from .offset_keypoint_octformer import OffsetKeypointOctFormer  # noqa: F401

@@ -109,6 +109,15 @@ KEYPOINT_STRAT_CFG = dict(
     rel_value=True, qkv_bias=True, stem=True, hidden_dim=256,
 )
 
+# the fork's OctFormer regression and per-point offset models (configs/my_dataset/keypoint_octformer.py:15-35 and
+# offset_keypoint_octformer.py:14-32), run at batch size 8
+KEYPOINT_OCTFORMER_CFG = dict(
+    type="KeypointOctFormer", in_channels=4, num_keypoints=6, fpn_channels=168, hidden_dim=256,
+    channels=(96, 192, 384, 384), num_blocks=(2, 2, 18, 2), num_heads=(6, 12, 24, 24), patch_size=26, stem_down=2,
+    head_up=2, dilation=4, drop_path=0.5, nempty=True, octree_depth=11, octree_full_depth=2, octree_scale_factor=10.24,
+)
+OFFSET_KEYPOINT_OCTFORMER_CFG = dict(KEYPOINT_OCTFORMER_CFG, type="OffsetKeypointOctFormer")
+
 # plumbing-size Swin3D: three levels, both head widths the kernel is built for (8 and 16)
 TINY_SWIN3D_CFG = dict(
     type="Swin3D-v1m1", in_channels=9, num_classes=13, base_grid_size=0.02, depths=[2, 2, 2], channels=[16, 32, 32],

@@ -176,6 +176,10 @@ SIGNATURES = {
     "ptv3_strat_attn_fwd": (c_int, [P, P, P, c_int64, P, P, P, P, P, P, P, P, c_int64, c_int, c_int, c_int, c_float,
                                     c_float, c_float, P, P]),
     "ptv3_ball_query": (c_int, [P, P, c_int, c_int64, c_float, c_int, P, P]),
+    "ptv3_octree_keys": (c_int, [P, P, c_int, c_int64, c_float, c_int, P, P, P]),
+    "ptv3_octree_attn_capable": (c_int, [c_int, c_int, c_int, c_int]),
+    "ptv3_octree_attn_fwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, P]),
+    "ptv3_octree_dwconv": (c_int, [P, P, P, P, P, P, c_int64, c_int, P]),
 }
 
 

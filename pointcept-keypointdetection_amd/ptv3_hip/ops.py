@@ -4,6 +4,7 @@ torch supplies device memory and the current HIP stream; all arithmetic happens 
 Every wrapper validates device / dtype / contiguity on the host before a pointer reaches a kernel.
 """
 import ctypes
+from types import SimpleNamespace
 
 import torch
 
@@ -1874,3 +1875,201 @@ def ball_query(radius, max_neighbor, xyz, offset, ends_host=None):
     lib.check(lib.ptv3_ball_query(_p(xyz), _p(offset), offset.shape[0], n, float(radius), int(max_neighbor), _p(idx),
                                   _stream()), "ptv3_ball_query")
     return idx
+
+
+# ---------------------------------------------------------------------------------------------
+# OctFormer: the octree of ocnn restated over the library's sort / segment / neighbour kernels, the fused octree
+# attention and the block's depthwise conv (parity with ocnn / dwconv unpinned)
+# ---------------------------------------------------------------------------------------------
+def key_to_xyz(key, depth):
+    """(n, 3) int32 cell coordinates and (n) int32 scene ids of octree keys (x in the highest bit of each triple)."""
+    xyz = torch.zeros((key.shape[0], 3), dtype=torch.int64, device=key.device)
+    for i in range(int(depth)):
+        for a in range(3):
+            xyz[:, a] |= ((key >> (3 * i + 2 - a)) & 1) << i
+    return xyz.int(), (key >> 48).int()
+
+
+class OctreeLevels:
+    """The non-empty nodes of depths min_depth..depth, every tensor in key order: keys[d] (n_d) int64, xyz[d] (n_d, 3)
+    int32, batch[d] (n_d) int32, nnum[d] host int, parent[d] (n_d) int64 rows of depth d-1, children[d] (n_d, 8) int32 rows
+    of depth d+1 by tap (x&1)*4 + (y&1)*2 + (z&1) (-1: empty), leaf (n points) int64 rows of depth `depth`, features
+    (n_depth, C) the leaf means.  Neighbour and deconvolution tables are built on first use."""
+
+    def __init__(self, depth, min_depth, batch_size):
+        self.depth, self.min_depth, self.batch_size = depth, min_depth, batch_size
+        self.keys, self.xyz, self.batch, self.nnum, self.parent, self.children = {}, {}, {}, {}, {}, {}
+        self.leaf = self.features = None
+        self._nbr, self._deconv, self._down = {}, {}, {}
+
+    def neighbors(self, d):
+        """(n_d, 27) int32, tap (dx+1)*9 + (dy+1)*3 + (dz+1), -1 where the cell is empty."""
+        if d not in self._nbr:
+            idx = torch.cat([self.batch[d].view(-1, 1), self.xyz[d]], dim=1).contiguous()
+            self._nbr[d] = subm_neighbors_blocks(idx, 3)[0]
+        return self._nbr[d]
+
+    def deconv_table(self, d):
+        """(n_{d+1}, 27) int32 rows of depth d, by the tap of the stride-2 3^3 convolution whose window 2P + {-1, 0, 1}
+        holds the fine cell: per axis offset 0 for an even coordinate, +1 for an odd one under its own parent and -1
+        for an odd one under the parent's +1 neighbour; -1 elsewhere (at most 8 entries of a row are set)."""
+        if d not in self._deconv:
+            nbr, par, xyz = self.neighbors(d), self.parent[d + 1], self.xyz[d + 1]
+            odd = (xyz & 1).bool()
+            tab = torch.full((xyz.shape[0], 27), -1, dtype=torch.int32, device=xyz.device)
+            for t in range(27):
+                o = (t // 9 - 1, t // 3 % 3 - 1, t % 3 - 1)
+                ok = torch.ones(xyz.shape[0], dtype=torch.bool, device=xyz.device)
+                src = 0
+                for a in range(3):
+                    ok &= ~odd[:, a] if o[a] == 0 else odd[:, a]
+                    src = src * 3 + (2 if o[a] == -1 else 1)
+                tab[:, t] = torch.where(ok, nbr[par, src], tab[:, t])
+            self._deconv[d] = tab
+        return self._deconv[d]
+
+    def down_plan(self, d):
+        """what down2_conv reads of a Down2Plan, for the kernel-2 / stride-2 convolution from depth d to d-1"""
+        if d not in self._down:
+            self._down[d] = SimpleNamespace(n=self.nnum[d], m_out=self.nnum[d - 1], child=self.children[d - 1])
+        return self._down[d]
+
+
+def octree_build(coord, feat, offset, scale_factor, depth, min_depth):
+    """OctreeLevels of ocnn's Octree.build_octree for the points coord (n, 3) fp32 / scale_factor with the features feat
+    (n, C) fp32 and the cumulative scene ends offset: ptv3_octree_keys, ONE sort of the leaf keys, one
+    ptv3_pool_segments per depth (the parents of sorted keys are runs) and ONE host read (the node counts, the
+    out-of-domain flag and the last offset).  A point outside -1 <= p < 1 raises ValueError (the reference would wrap it silently)."""
+    _chk(coord, "coord", torch.float32, 2)
+    _chk(feat, "feat", torch.float32, 2)
+    _chk(offset, "offset", (torch.int32, torch.int64), 1)
+    n, dev = coord.shape[0], coord.device
+    depth, min_depth = int(depth), int(min_depth)
+    if coord.shape[1] != 3 or feat.shape[0] != n or not 1 <= min_depth <= depth <= 16:
+        raise RuntimeError("octree_build: coord (n, 3), feat (n, C) and 1 <= min_depth <= depth <= 16 expected")
+    num_scenes = offset.shape[0]
+    off32 = offset if offset.dtype == torch.int32 else offset.int()
+    key = torch.empty(n, dtype=torch.int64, device=dev)
+    levels = list(range(depth, min_depth - 1, -1))
+    counts = torch.zeros(len(levels) + 1, dtype=torch.int32, device=dev)   # [n_d per level..., flag]
+    lib.check(lib.ptv3_octree_keys(_p(coord), _p(off32), num_scenes, n, float(scale_factor), depth, _p(key),
+                                   _p(counts) + 4 * len(levels), _stream()), "ptv3_octree_keys")
+    order = argsort_codes(key.view(1, -1), 63)[0][0]
+    ws_bytes = lib.ptv3_pool_workspace_bytes(n)
+    ws = _ws(ws_bytes, dev)
+    cluster, seg = {}, {}
+    for i, d in enumerate(levels):
+        cluster[d] = torch.empty(n, dtype=torch.int64, device=dev)
+        seg[d] = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        lib.check(lib.ptv3_pool_segments(_p(key), _p(order), n, 3 * (depth - d), None, _p(cluster[d]), _p(seg[d]),
+                                         _p(counts) + 4 * i, None, _p(ws), ws_bytes, _stream()), "ptv3_pool_segments")
+    host = torch.cat([counts, off32[-1:]]).tolist()   # the forward's one host read
+    if host.pop() != n:
+        raise ValueError(f"octree_build: the offsets do not end at the {n} points")
+    if host[-1]:
+        raise ValueError(f"octree_build: a point lies outside -1 <= coord / {scale_factor} < 1 (the octree's domain)")
+    oct = OctreeLevels(depth, min_depth, num_scenes)
+    for i, d in enumerate(levels):
+        n_d = host[i]
+        seg[d] = seg[d][:n_d + 1]
+        head = order[seg[d][:n_d].long()]
+        oct.nnum[d] = n_d
+        lead = key[head]
+        oct.keys[d] = ((lead >> 48) << 48) | ((lead & ((1 << 48) - 1)) >> (3 * (depth - d)))   # the scene id stays
+        oct.xyz[d], oct.batch[d] = key_to_xyz(oct.keys[d], d)
+        if d < depth:
+            # head of a run of depth d+1 -> its run of depth d
+            oct.parent[d + 1] = cluster[d][order[seg[d + 1][:host[i - 1]].long()]]
+            child = torch.full((n_d, 8), -1, dtype=torch.int32, device=dev)
+            child[oct.parent[d + 1], oct.keys[d + 1] & 7] = torch.arange(host[i - 1], dtype=torch.int32, device=dev)
+            oct.children[d] = child
+    oct.leaf = cluster[depth]
+    cnt = (seg[depth][1:] - seg[depth][:-1]).float().unsqueeze(1)
+    oct.features = segment_sum(feat, order, seg[depth], host[0]) / cnt
+    return oct
+
+
+def octree_attention_torch(qkv, xyz, batch, rpe_table, heads, patch, dilation, pos_bnd, scale, pad_row=None):
+    """OctreeAttention.forward between qkv and proj (octformer_v1m1_base.py:230-257) as the reference composes it: the
+    padded copy (padding rows carry pad_row, the bias of qkv, scene id -1 and coordinates 0), the dilation transpose,
+    the gathered RPE, the -1e3 mask and a softmax.  Any device, differentiable: the training and unfused path, and what
+    the kernel is tested and measured against."""
+    n_t, c3 = qkv.shape
+    c, k, d, h = c3 // 3, int(patch), int(dilation), int(heads)
+    pad = -n_t % (k * d)
+    if pad:
+        row = qkv.new_zeros(c3) if pad_row is None else pad_row.to(qkv.dtype)
+        qkv = torch.cat([qkv, row.expand(pad, c3)])
+        xyz = torch.cat([xyz, xyz.new_zeros((pad, 3))])
+        batch = torch.cat([batch, batch.new_full((pad,), -1)])
+
+    data = (qkv.view(-1, k, d, c3).transpose(1, 2) if d > 1 else qkv).reshape(-1, k, c3)
+    pos = (xyz.view(-1, k, d, 3).transpose(1, 2) if d > 1 else xyz).reshape(-1, k, 3).long()
+    scene = (batch.view(-1, k, d).transpose(1, 2) if d > 1 else batch).reshape(-1, k).long()
+    q, key, v = data.reshape(-1, k, 3, h, c // h).permute(2, 0, 3, 1, 4)
+    attn = (q * scale) @ key.transpose(-2, -1)
+    rel = pos.unsqueeze(2) - pos.unsqueeze(1)
+    rpe_num = 2 * pos_bnd + 1
+    idx = rel.clamp(-pos_bnd, pos_bnd) + (pos_bnd + torch.arange(3, device=rel.device) * rpe_num)
+    bias = rpe_table.index_select(0, idx.reshape(-1)).view(idx.shape + (-1,)).sum(3)
+    attn = attn + bias.permute(0, 3, 1, 2)
+    mask = scene.unsqueeze(2) - scene.unsqueeze(1)
+    attn = attn + mask.masked_fill(mask != 0, -1000).unsqueeze(1)
+    out = (torch.softmax(attn, dim=-1) @ v).transpose(1, 2).reshape(-1, c)
+    if d > 1:
+        out = out.view(-1, d, k, c).transpose(1, 2).reshape(-1, c)
+    return out[:n_t]
+
+
+def octree_attn_capable(c, heads, patch, dilation):
+    return bool(lib.ptv3_octree_attn_capable(int(c), int(heads), int(patch), int(dilation)))
+
+
+def octree_attention(qkv, xyz, batch, rpe_table, heads, patch, dilation, pos_bnd, scale, pad_row=None, fused=True):
+    """out (n_t, C) of qkv (n_t, 3C) in node order: ptv3_octree_attn_fwd when it covers the shape and nothing needs a
+    gradient (the kernel skips the keys the reference masks with -1e3, so it never reads pad_row), else
+    octree_attention_torch."""
+    needs_grad = torch.is_grad_enabled() and (qkv.requires_grad or rpe_table.requires_grad)
+    if fused and qkv.is_cuda and not needs_grad and qkv.dtype == torch.float32:
+        _chk(qkv, "qkv", torch.float32, 2)
+        _chk(xyz, "xyz", torch.int32, 2)
+        _chk(batch, "batch", torch.int32, 1)
+        table = rpe_table.detach()
+        _chk(table, "rpe_table", torch.float32, 2)
+        n_t, c = qkv.shape[0], qkv.shape[1] // 3
+        if qkv.shape[1] != 3 * c or tuple(xyz.shape) != (n_t, 3) or batch.shape[0] != n_t or \
+                tuple(table.shape) != (3 * (2 * pos_bnd + 1), heads):
+            raise RuntimeError("octree_attention: shape mismatch")
+        out = torch.empty((n_t, c), dtype=torch.float32, device=qkv.device)
+        rc = lib.ptv3_octree_attn_fwd(_p(qkv), _p(xyz), _p(batch), _p(table), _p(out), n_t, c, int(heads), int(patch),
+                                      int(dilation), int(pos_bnd), float(scale), _stream())
+        if rc != 3:   # PTV3_ERR_UNSUPPORTED: a shape for the composition
+            lib.check(rc, "ptv3_octree_attn_fwd")
+            return out
+    return octree_attention_torch(qkv, xyz, batch, rpe_table, heads, patch, dilation, pos_bnd, scale, pad_row)
+
+
+def octree_dwconv_torch(x, w, nbr, bn_scale, bn_shift):
+    """x + (sum_t w[t] * x[nbr[:, t]]) * bn_scale + bn_shift by one gather per tap (any device, differentiable)."""
+    xp = torch.cat([x, x.new_zeros((1, x.shape[1]))])
+    idx = torch.where(nbr >= 0, nbr, x.shape[0]).long()
+    acc = torch.zeros_like(x)
+    for t in range(27):
+        acc = acc + xp[idx[:, t]] * w[t]
+    return x + (acc * bn_scale + bn_shift)
+
+
+def octree_dwconv(x, w, nbr, bn_scale, bn_shift):
+    """ptv3_octree_dwconv: cpe(data) + data of an OctFormerBlock in eval; w (27, C) or the (27, 1, C) parameter."""
+    _chk(x, "x", torch.float32, 2)
+    _chk(w, "w", torch.float32)
+    _chk(nbr, "nbr", torch.int32, 2)
+    _chk(bn_scale, "bn_scale", torch.float32, 1)
+    _chk(bn_shift, "bn_shift", torch.float32, 1)
+    n, c = x.shape
+    if w.numel() != 27 * c or tuple(nbr.shape) != (n, 27) or bn_scale.numel() != c or bn_shift.numel() != c:
+        raise RuntimeError("octree_dwconv: shape mismatch")
+    out = torch.empty_like(x)
+    lib.check(lib.ptv3_octree_dwconv(_p(x), _p(w), _p(nbr), _p(bn_scale), _p(bn_shift), _p(out), n, c, _stream()),
+              "ptv3_octree_dwconv")
+    return out
