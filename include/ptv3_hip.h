@@ -552,7 +552,8 @@ int ptv3_adamw_fill_first_tile(void* entry_host, int first_tile);
  * address stored in the table.  torch's autograd leaves a new gradient tensor on each parameter after
  * zero_grad(set_to_none=True) (no zero fill, no accumulate-add per parameter); the addresses travel as kernel arguments,
  * 256 tensors per launch, so the table is neither rebuilt nor re-uploaded.  first_block_host (ntensors): the
- * first_block given to ptv3_adamw_fill_entry for every entry (required with grads_host). */
+ * first_block given to ptv3_adamw_fill_entry for every entry (required with grads_host).  A gradient address may be
+ * NULL only for an entry of zero elements (it owns no block); for any other entry the call is refused. */
 int ptv3_adamw_step(const void* table_dev, int ntensors, int total_blocks, const float* lr_host,
                     const float* wd_host, int ngroups, float beta1, float beta2, float eps, int64_t step,
                     float grad_scale, const int32_t* first_block_host, const void* const* grads_host, int total_tiles,

@@ -34,7 +34,8 @@ template <bool PTRS>
 __global__ void __launch_bounds__(256) adamw_kernel(const AdamWTensor* __restrict__ tab, int tensor_lo, int tensor_hi,
                                                      int block_base, AdamWGrads gp, AdamWGroups grp, float beta1,
                                                      float beta2, float eps, float bc1, float rsqrt_bc2,
-                                                     float grad_scale, float step_no) {
+                                                     float grad_scale, float step_no, float log_beta1,
+                                                     float log_beta2) {
   // find the tensor owning this block (entries tensor_lo .. tensor_hi of the table)
   const int blk = block_base + (int)blockIdx.x;
   int lo = tensor_lo, hi = tensor_hi;
@@ -47,9 +48,11 @@ __global__ void __launch_bounds__(256) adamw_kernel(const AdamWTensor* __restric
   const int64_t base = (int64_t)(blk - t.first_block) * ADAMW_CHUNK;
   const float lr = grp.lr[t.group], wd = grp.wd[t.group];
   if (t.step_lag != 0) {  // this tensor's own step count (block-uniform branch)
+    // 1 - beta^own as -expm1(own * log(beta)), log(beta) from the host in double: 1 - powf(beta, own) cancels for a small
+    // own count (beta2 = 0.999, own = 2: half an ulp of the power is 1.5e-5 of bc2, 5 E of tests/adamw_ref.py in p)
     const float own = step_no - (float)t.step_lag;
-    bc1 = 1.0f - powf(beta1, own);
-    rsqrt_bc2 = rsqrtf(1.0f - powf(beta2, own));
+    bc1 = -expm1f(own * log_beta1);
+    rsqrt_bc2 = rsqrtf(-expm1f(own * log_beta2));
   }
   const float step = lr / bc1;
   const float decay = 1.0f - lr * wd;
@@ -232,7 +235,9 @@ static int adamw_runs(int ntensors, int total_blocks, const int32_t* first_block
     const int t1 = t0 + ADAMW_PTRS < ntensors ? t0 + ADAMW_PTRS : ntensors;
     AdamWGrads gp{};
     for (int i = t0; i < t1; ++i) {
-      PTV3_REQUIRE(grads_host[i] != nullptr, "adamw: gradient %d is NULL", i);
+      // a zero-element tensor (torch.empty(0): its data_ptr() is NULL) owns no block, so no block ever reads its entry
+      const int next = i + 1 < ntensors ? first_block_host[i + 1] : total_blocks;
+      PTV3_REQUIRE(grads_host[i] != nullptr || next == first_block_host[i], "adamw: gradient %d is NULL", i);
       gp.g[i - t0] = (const float*)grads_host[i];
     }
     const int b0 = first_block_host[t0], b1 = t1 < ntensors ? first_block_host[t1] : total_blocks;
@@ -252,16 +257,17 @@ extern "C" int ptv3_adamw_step(const void* table_dev, int ntensors, int total_bl
   for (int i = 0; i < 8; ++i) { grp.lr[i] = i < ngroups ? lr_host[i] : 0.f; grp.wd[i] = i < ngroups ? wd_host[i] : 0.f; }
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const float lb1 = (float)log((double)beta1), lb2 = (float)log((double)beta2);   // for the step-lag branch
   const AdamWTensor* tab = (const AdamWTensor*)table_dev;
   hipStream_t s = (hipStream_t)stream;
   const int rc = adamw_runs(ntensors, total_blocks, first_block_host, grads_host,
                             [&](bool ptrs, int lo, int hi, int b0, int nb, const AdamWGrads& gp) {
     if (ptrs)
       hipLaunchKernelGGL(adamw_kernel<true>, dim3((unsigned)nb), dim3(256), 0, s, tab, lo, hi, b0, gp, grp, beta1, beta2,
-                         eps, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, (float)step);
+                         eps, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, (float)step, lb1, lb2);
     else
       hipLaunchKernelGGL(adamw_kernel<false>, dim3((unsigned)nb), dim3(256), 0, s, tab, lo, hi, b0, gp, grp, beta1, beta2,
-                         eps, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, (float)step);
+                         eps, (float)bc1, (float)(1.0 / sqrt(bc2)), grad_scale, (float)step, lb1, lb2);
   });
   if (rc != PTV3_OK) return rc;
   if (total_tiles > 0) {
