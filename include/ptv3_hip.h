@@ -955,6 +955,56 @@ int ptv3_octree_attn_fwd(const float* qkv, const int32_t* xyz, const int32_t* ba
 int ptv3_octree_dwconv(const float* x, const float* w, const int32_t* nbr, const float* bn_scale, const float* bn_shift,
                        float* out, int64_t n, int c, void* stream);
 
+/* ---- segmentation losses -------------------------------------------------------------------------
+ * A row is VALID when labels[i] != ignore_index and 0 <= labels[i] < C; every other row is ignored (the reference
+ * faults on an out-of-range label).  logits (n, C) fp32 row-major, labels (n) int64; 2 <= C <= 1024, n * C < 2^31,
+ * 16-byte aligned buffers, else PTV3_ERR_ARG before any launch.  Nothing is read back; no atomics; two runs on the same
+ * input are bitwise equal.
+ *
+ * ptv3_lovasz_fwd: LovaszLoss(mode="multiclass").forward of pointcept/models/losses/lovasz.py:241-257, that is
+ *   y_pred.softmax(1), _flatten_probas (:167-184), the per-class loop of _lovasz_softmax_flat (:118-164: labels.unique(),
+ *   fg, errors, torch.sort, fg[perm], the dot) and _lovasz_grad (:22-33), without the host reads of unique(), of
+ *   `fg.sum() == 0` and of the boolean-mask compaction.  Per class c: err_i = |fg_i - p_ic| over the valid rows, sorted
+ *   descending (ties by point index: a stable radix sort of the inverted float bits, not-valid rows last); with
+ *   F = the running foreground count at sorted position i (1-based), G = the class's foreground count, I = G - F,
+ *   U = G + i - F, the weight is 1/U on a foreground row, I / (U (U - 1)) on a background row, 1 - I/U at i = 1 on a
+ *   background row: jaccard[i] - jaccard[i-1] of :28-32 in closed form, evaluated in float64 from integers (the
+ *   reference's fp32 difference of near-equal numbers is off by tens of percent at a few thousand rows).
+ *   out[0] = loss_weight * mean over the classes with G > 0 of sum_i err_i g_i; 0 when no row is valid (the reference
+ *   returns an empty tensor there).  weight (n, C) fp32 = g in point order, 0 on a row that is not valid (kept for the
+ *   backward); order (C, n) int64 = the per-class sorted order; count (C + 1) int32 = G_c, then the number of present
+ *   classes.  workspace: ptv3_lovasz_workspace_bytes(n, C), 16-byte aligned.  ptv3_lovasz_scan_tile(): positions per
+ *   workgroup of the scan.  Launches: prep, the radix passes of ptv3_argsort_i64 (k = C, end_bit 33), tile count, tile
+ *   scan, apply, finish.
+ * ptv3_lovasz_bwd: autograd of the above (softmax backward with the weights held constant, as torch's sort/gather
+ *   gives): dP_c = dloss[0] * loss_weight / n_present * weight[i, c] * (fg ? -1 : +1) for a present class, 0 otherwise;
+ *   dlogits[i, j] = p_j (dP_j - sum_k p_k dP_k); zeros on a row that is not valid.  One launch.
+ *
+ * ptv3_focal_fwd / ptv3_focal_bwd: FocalLoss.forward of pointcept/models/losses/misc.py:123-172 (the multi-class
+ *   sigmoid form) and its autograd.  Per element, t the one-hot target: s = sigmoid(x), q = (1 - s) t + s (1 - t),
+ *   a = alpha[c] t + (1 - alpha[c])(1 - t), bce = max(x, 0) - x t + log1p(exp(-|x|)), L = a q^gamma bce.
+ *   out[0] = loss_weight * sum L over the valid rows, divided by n_valid * C with mean != 0 (:168-169); with mean == 0
+ *   the plain sum (the reference calls a missing method there, :170-171).  0 when no row is valid (:148-149).
+ *   nvalid[0] int32 = n_valid.  alpha (C) fp32 on the device; gamma >= 0.  Two launches (fixed chunks -> slab, one
+ *   finishing workgroup in float64).  workspace: ptv3_focal_workspace_bytes(n, C), 16-byte aligned.
+ *   bwd: dlogits = dloss[0] * loss_weight (/ (n_valid C)) * a q^gamma (gamma (1 - q)(1 - 2t) bce + (s - t)), zeros on a
+ *   row that is not valid.  One launch. */
+int ptv3_lovasz_scan_tile(void);
+size_t ptv3_lovasz_workspace_bytes(int64_t n, int C);
+int ptv3_lovasz_fwd(const float* logits, const int64_t* labels, int64_t n, int C, int64_t ignore_index,
+                    float loss_weight, float* out, float* weight, int64_t* order, int32_t* count, void* workspace,
+                    size_t workspace_bytes, void* stream);
+int ptv3_lovasz_bwd(const float* dloss, const float* logits, const int64_t* labels, const float* weight,
+                    const int32_t* count, int64_t n, int C, int64_t ignore_index, float loss_weight, float* dlogits,
+                    void* stream);
+size_t ptv3_focal_workspace_bytes(int64_t n, int C);
+int ptv3_focal_fwd(const float* logits, const int64_t* labels, const float* alpha, int64_t n, int C,
+                   int64_t ignore_index, float gamma, float loss_weight, int mean, float* out, int32_t* nvalid,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int ptv3_focal_bwd(const float* dloss, const float* logits, const int64_t* labels, const float* alpha,
+                   const int32_t* nvalid, int64_t n, int C, int64_t ignore_index, float gamma, float loss_weight, int mean,
+                   float* dlogits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,2 +1,3 @@
 from .builder import LOSSES, Criteria, build_criteria  # noqa: F401
-from .misc import CrossEntropyLoss  # noqa: F401
+from .misc import CrossEntropyLoss, FocalLoss  # noqa: F401
+from .lovasz import LovaszLoss  # noqa: F401

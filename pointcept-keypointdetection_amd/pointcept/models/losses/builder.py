@@ -1,6 +1,8 @@
 """Loss registry + the `Criteria` aggregate the segmentor wrappers call (interface of the reference's
-pointcept/models/losses/builder.py).  Losses are plain torch and sit outside the MI355X hot path
-(SURVEY.md section 2a row 9); the registry exists so DefaultSegmentorV2 configs build unchanged."""
+pointcept/models/losses/builder.py).  CrossEntropyLoss is plain torch (one fused launch there already); LovaszLoss and
+FocalLoss run HIP kernels on a GPU prediction (csrc/seg_loss.hip), because the reference's
+Lovasz composition is hundreds of small launches and one host read per class.  The registry exists so
+DefaultSegmentor / DefaultSegmentorV2 configs build unchanged."""
 from functools import reduce
 
 from pointcept.utils.registry import Registry

@@ -426,6 +426,54 @@ def vote_loss(votes, coord, target, offset, vote_radius, scale=None):
     return VoteLossFn.apply(votes, coord, target, offset, vote_radius, scale)
 
 
+class LovaszSoftmaxFn(Function):
+    """Multiclass Lovasz-Softmax (losses/lovasz.py:118-164) on fp32 logits (N, C): forward = ops.lovasz_softmax, which
+    leaves the Lovasz weights in point order; backward = one launch.  Saved besides the inputs: weight and count."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, loss_weight):
+        logits, labels = logits.contiguous(), labels.contiguous()
+        out, weight, _order, count = ops.lovasz_softmax(logits, labels, ignore_index, loss_weight)
+        ctx.save_for_backward(logits, labels, weight, count)
+        ctx.ignore_index, ctx.loss_weight = ignore_index, loss_weight
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, labels, weight, count = ctx.saved_tensors
+        return ops.lovasz_softmax_bwd(dloss.float().contiguous(), logits, labels, weight, count, ctx.ignore_index,
+                                      ctx.loss_weight), None, None, None
+
+
+def lovasz_softmax(logits, labels, ignore_index=None, loss_weight=1.0):
+    """-> loss, 0-d fp32 with grad."""
+    return LovaszSoftmaxFn.apply(logits, labels, ignore_index, loss_weight)
+
+
+class FocalLossFn(Function):
+    """Multi-class sigmoid focal loss (losses/misc.py:123-172) on fp32 logits (N, C): two launches forward, one backward
+    (everything recomputed from the inputs; only the count of valid rows is kept, for the mean's divisor)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, alpha, gamma, ignore_index, loss_weight, reduction):
+        logits, labels = logits.contiguous(), labels.contiguous()
+        out, nvalid = ops.focal_loss(logits, labels, alpha, gamma, ignore_index, loss_weight, reduction)
+        ctx.save_for_backward(logits, labels, alpha, nvalid)
+        ctx.args = (gamma, ignore_index, loss_weight, reduction)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        logits, labels, alpha, nvalid = ctx.saved_tensors
+        return (ops.focal_loss_bwd(dloss.float().contiguous(), logits, labels, alpha, nvalid, *ctx.args),
+                None, None, None, None, None, None)
+
+
+def focal_loss(logits, labels, alpha, gamma=2.0, ignore_index=-1, loss_weight=1.0, reduction="mean"):
+    """-> loss, 0-d fp32 with grad; alpha (C) fp32 on the logits' device."""
+    return FocalLossFn.apply(logits, labels, alpha, gamma, ignore_index, loss_weight, reduction)
+
+
 def linear(x, weight, bias=None):
     return LinearFn.apply(x, weight, bias)
 

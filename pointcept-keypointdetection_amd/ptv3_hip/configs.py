@@ -26,6 +26,15 @@ FORK_CFG = dict(
 # configs/nuscenes/semseg-pt-v3m1-0-base.py): same widths as the fork, enable_flash=True, 1024-point patches
 SEMSEG_CFG = dict(FORK_CFG, enable_flash=True)
 
+# the fork's segmentation criteria (configs/pigseg/semseg-{ptv3,swin3d,octformer}-v1m1-0-base.py share this list) and
+# the `model` dict of configs/pigseg/semseg-ptv3-v1m1-0-base.py:34-70
+PIGSEG_CRITERIA = [
+    dict(type="FocalLoss", gamma=2.0, alpha=[0.1, 0.9], loss_weight=1.0, ignore_index=-1),
+    dict(type="LovaszLoss", mode="multiclass", loss_weight=3.0, ignore_index=-1),
+]
+PIGSEG_PTV3_CFG = dict(type="DefaultSegmentorV2", num_classes=2, backbone_out_channels=64,
+                       backbone=dict(type="PT-v3m1", **FORK_CFG), criteria=PIGSEG_CRITERIA)
+
 # "PT-v3m2" (point_transformer_v3m2_sonata.py) plumbing-size config: GridPooling, LayerScale, LayerNorm stem
 TINY_M2_CFG = dict(
     in_channels=4, order=ORDERS, stride=(2, 2, 2, 2),

@@ -180,6 +180,13 @@ SIGNATURES = {
     "ptv3_octree_attn_capable": (c_int, [c_int, c_int, c_int, c_int]),
     "ptv3_octree_attn_fwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     "ptv3_octree_dwconv": (c_int, [P, P, P, P, P, P, c_int64, c_int, P]),
+    "ptv3_lovasz_scan_tile": (c_int, []),
+    "ptv3_lovasz_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "ptv3_lovasz_fwd": (c_int, [P, P, c_int64, c_int, c_int64, c_float, P, P, P, P, P, c_size_t, P]),
+    "ptv3_lovasz_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int64, c_float, P, P]),
+    "ptv3_focal_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "ptv3_focal_fwd": (c_int, [P, P, P, c_int64, c_int, c_int64, c_float, c_float, c_int, P, P, P, c_size_t, P]),
+    "ptv3_focal_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int64, c_float, c_float, c_int, P, P]),
 }
 
 

@@ -1164,6 +1164,102 @@ def vote_loss_bwd(dloss, votes, coord, target, offset, count, vote_radius):
 
 
 # ---------------------------------------------------------------------------------------------
+# segmentation losses
+# ---------------------------------------------------------------------------------------------
+SEG_LOSS_MAX_CLASSES = 1024
+NO_IGNORE = -2 ** 63          # ignore_index=None: no label equals it
+
+
+def seg_loss_capable(n, c):
+    """Shapes ptv3_lovasz_* / ptv3_focal_* cover: 2 <= C <= 1024 and N * C < 2^31."""
+    return 2 <= c <= SEG_LOSS_MAX_CLASSES and n * c < 2 ** 31
+
+
+def lovasz_scan_tile():
+    return int(lib.ptv3_lovasz_scan_tile())
+
+
+def _seg_args(who, logits, labels):
+    _chk(logits, f"{who}: logits", torch.float32, 2)
+    _chk(labels, f"{who}: labels", torch.int64, 1)
+    n, c = logits.shape
+    if labels.shape[0] != n:
+        raise RuntimeError(f"{who}: logits {tuple(logits.shape)} / labels {tuple(labels.shape)}: expected (N, C), (N)")
+    return n, c
+
+
+def lovasz_softmax(logits, labels, ignore_index=None, loss_weight=1.0):
+    """Multiclass Lovasz-Softmax of losses/lovasz.py:118-164 + :241-257 without a host read -> (out (1) fp32 = the loss,
+    weight (N, C) fp32 in point order, order (C, N) int64 per-class descending order, count (C + 1) int32 = per-class
+    foreground counts then the number of present classes)."""
+    n, c = _seg_args("lovasz_softmax", logits, labels)
+    dev = logits.device
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    weight = torch.empty((n, c), dtype=torch.float32, device=dev)
+    order = torch.empty((c, n), dtype=torch.int64, device=dev)
+    count = torch.empty(c + 1, dtype=torch.int32, device=dev)
+    nbytes = lib.ptv3_lovasz_workspace_bytes(n, c)
+    ws = _ws(nbytes, dev)
+    ign = NO_IGNORE if ignore_index is None else int(ignore_index)
+    lib.check(lib.ptv3_lovasz_fwd(_p(logits), _p(labels), n, c, ign, float(loss_weight), _p(out), _p(weight), _p(order),
+                                  _p(count), _p(ws), nbytes, _stream()), "ptv3_lovasz_fwd")
+    return out, weight, order, count
+
+
+def lovasz_softmax_bwd(dloss, logits, labels, weight, count, ignore_index=None, loss_weight=1.0):
+    """dlogits (N, C) fp32 of lovasz_softmax: the softmax backward with the saved weights."""
+    n, c = _seg_args("lovasz_softmax_bwd", logits, labels)
+    _chk(dloss, "dloss", torch.float32)
+    _chk(weight, "weight", torch.float32, 2)
+    _chk(count, "count", torch.int32, 1)
+    if dloss.numel() != 1 or tuple(weight.shape) != (n, c) or count.shape[0] != c + 1:
+        raise RuntimeError("lovasz_softmax_bwd: dloss must hold one value, weight be (N, C) and count C + 1")
+    dlogits = torch.empty_like(logits)
+    ign = NO_IGNORE if ignore_index is None else int(ignore_index)
+    lib.check(lib.ptv3_lovasz_bwd(_p(dloss), _p(logits), _p(labels), _p(weight), _p(count), n, c, ign,
+                                  float(loss_weight), _p(dlogits), _stream()), "ptv3_lovasz_bwd")
+    return dlogits
+
+
+def _focal_alpha(alpha, c):
+    _chk(alpha, "alpha", torch.float32, 1)
+    if alpha.shape[0] != c:
+        raise RuntimeError(f"focal_loss: alpha holds {alpha.shape[0]} values for {c} classes")
+
+
+def focal_loss(logits, labels, alpha, gamma=2.0, ignore_index=-1, loss_weight=1.0, reduction="mean"):
+    """Multi-class sigmoid focal loss of losses/misc.py:123-172 -> (out (1) fp32 = the loss, nvalid (1) int32).
+    alpha (C) fp32 on the device."""
+    n, c = _seg_args("focal_loss", logits, labels)
+    _focal_alpha(alpha, c)
+    dev = logits.device
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    nvalid = torch.empty(1, dtype=torch.int32, device=dev)
+    nbytes = lib.ptv3_focal_workspace_bytes(n, c)
+    ws = _ws(nbytes, dev)
+    ign = NO_IGNORE if ignore_index is None else int(ignore_index)
+    lib.check(lib.ptv3_focal_fwd(_p(logits), _p(labels), _p(alpha), n, c, ign, float(gamma), float(loss_weight),
+                                 int(reduction == "mean"), _p(out), _p(nvalid), _p(ws), nbytes, _stream()),
+              "ptv3_focal_fwd")
+    return out, nvalid
+
+
+def focal_loss_bwd(dloss, logits, labels, alpha, nvalid, gamma=2.0, ignore_index=-1, loss_weight=1.0, reduction="mean"):
+    """dlogits (N, C) fp32 of focal_loss."""
+    n, c = _seg_args("focal_loss_bwd", logits, labels)
+    _focal_alpha(alpha, c)
+    _chk(dloss, "dloss", torch.float32)
+    _chk(nvalid, "nvalid", torch.int32, 1)
+    if dloss.numel() != 1 or nvalid.numel() != 1:
+        raise RuntimeError("focal_loss_bwd: dloss and nvalid must hold one value each")
+    dlogits = torch.empty_like(logits)
+    ign = NO_IGNORE if ignore_index is None else int(ignore_index)
+    lib.check(lib.ptv3_focal_bwd(_p(dloss), _p(logits), _p(labels), _p(alpha), _p(nvalid), n, c, ign, float(gamma),
+                                 float(loss_weight), int(reduction == "mean"), _p(dlogits), _stream()), "ptv3_focal_bwd")
+    return dlogits
+
+
+# ---------------------------------------------------------------------------------------------
 # pointops
 # ---------------------------------------------------------------------------------------------
 def knn_query(nsample, xyz, offset, new_xyz, new_offset):
