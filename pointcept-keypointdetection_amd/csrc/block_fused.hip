@@ -21,22 +21,55 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
+#include <type_traits>
 #include "profile.h"
 #include "../../include/ptv3_hip.h"
 
 namespace ptv3 {
 
 template <typename T> struct WPad { static constexpr int V = 16 / sizeof(T); };
+// slab loads (16 bytes each) a lane keeps in flight in block_head_kernel = channel groups x slabs per batch (slab_sum,
+// common.h): 8, which leaves the kernel its waves per SIMD; 4 for fp32 at C = 64, where 8 would cost one (74 > 72 registers)
+template <typename T, int NT> struct HeadSlab { static constexpr int LOADS = sizeof(T) == 4 && NT == 4 ? 4 : 8; };
+constexpr int COOP_SLAB_LOADS = 8;   // the same in block_head_coop_kernel
 
+// Copies a rows x cols matrix into LDS rows of stride ld.  A thread fetches a batch of 16-byte chunks before its first
+// LDS write: one chunk per iteration is `load; s_waitcnt vmcnt(0); ds_write`, a memory round trip per chunk (DESIGN §0
+// rule 6).  A slot past the end copies the last chunk once more (the same bytes to the same place): with a branch
+// around the write the compiler sinks the load into it, and a load behind a branch waits for vmcnt(0) (rule 2).
 template <typename T>
 __device__ __forceinline__ void stage_matrix(T* dst, const T* __restrict__ src, int rows, int cols, int ld) {
   typedef typename Frag<T>::type FR;
   constexpr int E = Frag<T>::E;
-  const int cpr = cols / E;
-  for (int u = threadIdx.x; u < rows * cpr; u += blockDim.x) {
-    const int r = u / cpr, ch = u % cpr;
-    *reinterpret_cast<FR*>(dst + r * ld + E * ch) = *reinterpret_cast<const FR*>(src + (int64_t)r * cols + E * ch);
-  }
+  const int cpr = cols / E, total = rows * cpr, nthreads = blockDim.x;
+  auto stage_pass = [&](const int u0, auto unroll_tag) {
+    constexpr int U = decltype(unroll_tag)::value;
+    FR reg[U];
+    int to[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = u0 + u * nthreads < total ? u0 + u * nthreads : total - 1;
+      to[u] = (i / cpr) * ld + E * (i % cpr);
+      reg[u] = *reinterpret_cast<const FR*>(src + (unsigned)(E * i));   // the source is dense: chunk i starts at E * i
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) *reinterpret_cast<FR*>(dst + to[u]) = reg[u];
+  };
+  // every thread runs every pass (the caller's barrier follows): 8 chunks each while more than 4 remain per thread
+  int base = 0;
+  for (; base + 4 * nthreads < total; base += 8 * nthreads) stage_pass(base + threadIdx.x, std::integral_constant<int, 8>{});
+  for (; base + nthreads < total; base += 4 * nthreads) stage_pass(base + threadIdx.x, std::integral_constant<int, 4>{});
+  if (base < total) stage_pass(base + threadIdx.x, std::integral_constant<int, 1>{});
+}
+
+// A per-channel vector goes to LDS in two steps: vec_fetch before the weight matrices are staged (element threadIdx.x,
+// clamped: n <= blockDim.x for all but a wide hidden bias), vec_put after them - its round trip is then the matrices'.
+__device__ __forceinline__ float vec_fetch(const float* __restrict__ src, int n) {
+  return src[(int)threadIdx.x < n ? (int)threadIdx.x : n - 1];
+}
+__device__ __forceinline__ void vec_put(float* dst, float v, const float* __restrict__ src, int n) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] = v;
+  for (int i = threadIdx.x + blockDim.x; i < n; i += blockDim.x) dst[i] = src[i];
 }
 
 template <typename T, int NT, bool WLDS>
@@ -57,17 +90,18 @@ __global__ void __launch_bounds__(256) block_head_kernel(HeadArgs a) {
   float* sVec = reinterpret_cast<float*>(head_smem + (WLDS ? (size_t)3 * C * (C + WPad<T>::V) * sizeof(T) : 0));
   const float *vg0 = sVec, *vb0 = sVec + C, *vg1 = sVec + 2 * C, *vb1 = sVec + 3 * C, *vbq = sVec + 4 * C,
               *vcb = sVec + 7 * C;
-  for (int i = threadIdx.x; i < C; i += 256) {
-    sVec[i] = a.g0[i]; sVec[C + i] = a.b0[i]; sVec[2 * C + i] = a.g1[i]; sVec[3 * C + i] = a.b1[i];
-    sVec[7 * C + i] = a.conv_bias ? a.conv_bias[i] : 0.f;
-  }
-  for (int i = threadIdx.x; i < 3 * C; i += 256) sVec[4 * C + i] = a.bqkv[i];
+  const float* cbias = a.conv_bias ? a.conv_bias : a.g0;   // fetched either way: no load behind a branch
+  const float fg0 = vec_fetch(a.g0, C), fb0 = vec_fetch(a.b0, C), fg1 = vec_fetch(a.g1, C), fb1 = vec_fetch(a.b1, C),
+              fcb = vec_fetch(cbias, C), fbq = vec_fetch(a.bqkv, 3 * C);
   if (WLDS) {   // the 3C x C qkv weight resident in LDS for all row blocks of this workgroup
     ldc = C + WPad<T>::V;
     T* sW = reinterpret_cast<T*>(head_smem);
     stage_matrix<T>(sW, w, 3 * C, C, ldc);
     w = sW;
   }
+  vec_put(sVec, fg0, a.g0, C); vec_put(sVec + C, fb0, a.b0, C); vec_put(sVec + 2 * C, fg1, a.g1, C);
+  vec_put(sVec + 3 * C, fb1, a.b1, C); vec_put(sVec + 4 * C, fbq, a.bqkv, 3 * C);
+  vec_put(sVec + 7 * C, a.conv_bias ? fcb : 0.f, cbias, C);
   __syncthreads();
   const int64_t nblocks = (a.m + 63) / 64;
   for (int64_t blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
@@ -78,18 +112,25 @@ __global__ void __launch_bounds__(256) block_head_kernel(HeadArgs a) {
   const T* sc = reinterpret_cast<const T*>(a.shortcut);
 
   f32x4 v[NT];
+  if (a.slab) {
+    // all NT channel groups of the row and a batch of slabs in flight together
+    int off[NT];
 #pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    const int ch = 16 * j + 4 * g;
-    if (a.slab) {
-      f32x4 acc = *reinterpret_cast<const f32x4*>(vcb + ch);
-      for (int z = 0; z < a.splits; ++z)
-        acc += *reinterpret_cast<const f32x4*>(a.slab + ((int64_t)z * a.m + rc) * C + ch);
+    for (int j = 0; j < NT; ++j) {
+      off[j] = (int)((rc * C + 16 * j + 4 * g) * sizeof(float));
+      v[j] = *reinterpret_cast<const f32x4*>(vcb + 16 * j + 4 * g);
+    }
+    slab_sum<NT, HeadSlab<T, NT>::LOADS / NT>(v, slab_rsrc(a.slab, a.m * C * sizeof(float), a.splits), off,
+                                       (int)(a.m * C * sizeof(float)), a.splits);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) v[j][r] = round_to<T>(acc[r]);
-    } else {
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[j][r] = round_to<T>(v[j][r]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
       float t[4];
-      unpack4<T>(*reinterpret_cast<const V4*>(reinterpret_cast<const T*>(a.x) + rc * C + ch), t);
+      unpack4<T>(*reinterpret_cast<const V4*>(reinterpret_cast<const T*>(a.x) + rc * C + 16 * j + 4 * g), t);
       v[j] = f32x4{t[0], t[1], t[2], t[3]};
     }
   }
@@ -176,13 +217,13 @@ __global__ void __launch_bounds__(256) block_tail_kernel(TailArgs a) {
     T* sW1 = sWp + C * ldc;
     T* sW2 = sW1 + a.hidden * ldc;
     float* sVec = reinterpret_cast<float*>(sW2 + C * ldh);   // 16-byte aligned: every part above is a multiple of 16 bytes
+    const float fbp = vec_fetch(a.bproj, C), fg2 = vec_fetch(a.g2, C), fb2 = vec_fetch(a.b2, C),
+                fbias2 = vec_fetch(a.bias2, C), fbias1 = vec_fetch(a.bias1, a.hidden);
     stage_matrix<T>(sWp, wp, C, C, ldc);
     stage_matrix<T>(sW1, w1, a.hidden, C, ldc);
     stage_matrix<T>(sW2, w2, C, a.hidden, ldh);
-    for (int i = threadIdx.x; i < C; i += 256) {
-      sVec[i] = a.bproj[i]; sVec[C + i] = a.g2[i]; sVec[2 * C + i] = a.b2[i]; sVec[3 * C + i] = a.bias2[i];
-    }
-    for (int i = threadIdx.x; i < a.hidden; i += 256) sVec[4 * C + i] = a.bias1[i];
+    vec_put(sVec, fbp, a.bproj, C); vec_put(sVec + C, fg2, a.g2, C); vec_put(sVec + 2 * C, fb2, a.b2, C);
+    vec_put(sVec + 3 * C, fbias2, a.bias2, C); vec_put(sVec + 4 * C, fbias1, a.bias1, a.hidden);
     __syncthreads();
     wp = sWp; w1 = sW1; w2 = sW2;
     vbp = sVec; vg2 = sVec + C; vb2 = sVec + 2 * C; vbias2 = sVec + 3 * C; vbias1 = sVec + 4 * C;
@@ -527,18 +568,26 @@ __global__ void __launch_bounds__(64 * Coop<C>::NW) block_head_coop_kernel(HeadA
     const int64_t rc = valid ? row : a.m - 1;
     const int c0 = ll * CPL;
     float v[CPL];
+    if (a.slab) {
+      constexpr int N4 = CPL / 4;
+      f32x4 acc[N4];
+      int off[N4];
 #pragma unroll
-    for (int e4 = 0; e4 < CPL / 4; ++e4) {
-      const int ch = c0 + 4 * e4;
-      if (a.slab) {
-        f32x4 acc = *reinterpret_cast<const f32x4*>(a.conv_bias + ch);
-        for (int z = 0; z < a.splits; ++z)
-          acc += *reinterpret_cast<const f32x4*>(a.slab + ((int64_t)z * a.m + rc) * C + ch);
+      for (int e4 = 0; e4 < N4; ++e4) {
+        off[e4] = (int)((rc * C + c0 + 4 * e4) * sizeof(float));
+        acc[e4] = *reinterpret_cast<const f32x4*>(a.conv_bias + c0 + 4 * e4);
+      }
+      slab_sum<N4, COOP_SLAB_LOADS / N4>(acc, slab_rsrc(a.slab, a.m * C * sizeof(float), a.splits), off,
+                                         (int)(a.m * C * sizeof(float)), a.splits);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[4 * e4 + r] = round_to<T>(acc[r]);
-      } else {
+      for (int e4 = 0; e4 < N4; ++e4)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[4 * e4 + r] = round_to<T>(acc[e4][r]);
+    } else {
+#pragma unroll
+      for (int e4 = 0; e4 < CPL / 4; ++e4) {
         float t[4];
-        unpack4<T>(*reinterpret_cast<const V4*>(reinterpret_cast<const T*>(a.x) + rc * C + ch), t);
+        unpack4<T>(*reinterpret_cast<const V4*>(reinterpret_cast<const T*>(a.x) + rc * C + c0 + 4 * e4), t);
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[4 * e4 + r] = t[r];
       }
@@ -860,6 +909,8 @@ extern "C" int ptv3_block_head(const void* x, const float* slab, int splits, con
   PTV3_REQUIRE(mode != 0, "block_head: c=%d not fusable", c);
   PTV3_REQUIRE((x != nullptr) != (slab != nullptr), "block_head: give the conv output OR its split-K slabs");
   PTV3_REQUIRE(slab == nullptr || (splits >= 1 && conv_bias != nullptr), "block_head: slabs need splits and the conv bias");
+  PTV3_REQUIRE(slab == nullptr || m * c * splits * 4 < SLAB_MAX_BYTES, "block_head: %d slabs of %lld x %d are 2 GiB or more",
+               splits, (long long)m, c);
   PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "block_head: bad dtype");
   if (m == 0) return PTV3_OK;
   hipStream_t s = (hipStream_t)stream;

@@ -58,6 +58,39 @@ template <> __device__ __forceinline__ void unpack4<__bf16>(s16x4 v, float* o) {
   o[0] = bf16_to_f32(v[0]); o[1] = bf16_to_f32(v[1]); o[2] = bf16_to_f32(v[2]); o[3] = bf16_to_f32(v[3]);
 }
 
+// acc[n] += slab z at byte offset off[n], for z = 0 .. splits-1 in that order: the fp32 split-K slabs of a GEMM,
+// `stride` bytes apart.  A rolled `for z` is one load and a full wait per slab (DESIGN §0 rule 6): the N * B loads
+// of a batch are issued together instead.  A partial last batch loads from the clamped last slab and drops the sum
+// with a select - a load behind a branch would wait for vmcnt(0) (rule 2), and adding 0.0f would turn a -0.0f sum
+// into +0.0f.  Through a buffer descriptor the slab's offset is a scalar and a load takes one address register,
+// not two; for that all slabs together stay below SLAB_MAX_BYTES (callers check).
+constexpr int64_t SLAB_MAX_BYTES = (int64_t)1 << 31;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t slab_rsrc(const float* slab, int64_t stride_bytes, int splits) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(slab), 0, (int)(stride_bytes * splits), 0x00020000);
+}
+template <int N, int B>
+__device__ __forceinline__ void slab_sum(f32x4 (&acc)[N], __amdgpu_buffer_rsrc_t slabs, const int (&off)[N],
+                                         int stride, int splits) {
+  for (int z0 = 0; z0 < splits; z0 += B) {
+    f32x4 t[B][N];
+#pragma unroll
+    for (int u = 0; u < B; ++u) {
+      const int zoff = (z0 + u < splits ? z0 + u : splits - 1) * stride;
+#pragma unroll
+      for (int n = 0; n < N; ++n)
+        t[u][n] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(slabs, off[n], zoff, 0));
+    }
+    __builtin_amdgcn_sched_barrier(0);  // or the scheduler sinks loads between the adds to save registers
+#pragma unroll
+    for (int u = 0; u < B; ++u)
+#pragma unroll
+      for (int n = 0; n < N; ++n) {
+        const f32x4 sum = acc[n] + t[u][n];
+        acc[n] = z0 + u < splits ? sum : acc[n];
+      }
+  }
+}
+
 template <typename T> __device__ __forceinline__ float to_f32(T v);
 template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
 template <> __device__ __forceinline__ float to_f32<__bf16>(__bf16 v) { return (float)v; }

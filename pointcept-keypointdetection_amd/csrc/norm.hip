@@ -6,6 +6,12 @@
 namespace ptv3 {
 
 constexpr int LN_MAXCH = 8;  // 4-element chunks held per lane -> c <= 64 lanes * 8 * 4 = 2048
+// slab loads (16 bytes each) a lane keeps in flight = chunks per lane x slabs per batch: as many as keep the kernel
+// at the waves per SIMD of the plain one.  16 with all 64 lanes on a row (80 registers, 6 waves), 12 with fewer lanes
+// or two chunks per lane (72, 7 waves), 8 at c = 4 (56, 8 waves) and from four chunks per lane on
+template <int LPR, int NK> struct LnSlab {
+  static constexpr int LOADS = LPR == 1 || NK > 2 ? 8 : LPR == 64 && NK == 1 ? 16 : 12;
+};
 
 template <int LPR>
 __device__ __forceinline__ float row_sum(float v) {
@@ -14,8 +20,10 @@ __device__ __forceinline__ float row_sum(float v) {
   return v;
 }
 
-// LPR lanes cooperate on one row (64/LPR rows per wave), 4 waves per block
-template <typename T, int LPR>
+// LPR lanes cooperate on one row (64/LPR rows per wave), 4 waves per block.
+// NK > 0: the input is the split-K slabs of the producing GEMM and a lane holds at most NK chunks (its own kernel:
+// the batch of slab loads in flight must not cost the plain kernel, which runs at large m, registers).
+template <typename T, int LPR, int NK = 0>
 __global__ void __launch_bounds__(256)
 layernorm_kernel(const T* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                  const T* __restrict__ res, T* __restrict__ y, const float* __restrict__ gamma2,
@@ -28,23 +36,31 @@ layernorm_kernel(const T* __restrict__ x, const float* __restrict__ gamma, const
   const int64_t row = ((int64_t)blockIdx.x * 4 + wave) * RPW + lane / LPR;
   const bool rv = row < m;
   const int nch = c / 4;  // chunks per row; lane takes chunks sub, sub+LPR, ...
-  float v[LN_MAXCH][4];
+  constexpr int KN = NK > 0 ? NK : LN_MAXCH;
+  float v[KN][4];
   float s = 0.f;
+  f32x4 acc[KN];
+  if constexpr (NK > 0) {
+    // the producing GEMM left split-K fp32 slabs: sum them in slab order, add its bias, round to T as the
+    // separate reduce kernel would have stored it.  Every lane loads (rows and chunks past the end from a clamped
+    // address) so that the loads of all chunks and of a whole batch of slabs are in flight together.
+    int off[NK];
 #pragma unroll
-  for (int k = 0; k < LN_MAXCH; ++k) {
+    for (int k = 0; k < NK; ++k) {
+      const int ch = sub + k * LPR < nch ? sub + k * LPR : 0;
+      off[k] = (int)(((rv ? row : m - 1) * c + 4 * ch) * sizeof(float));
+      acc[k] = *reinterpret_cast<const f32x4*>(slab_bias + 4 * ch);
+    }
+    const int64_t stride = m * c * sizeof(float);
+    slab_sum<NK, LnSlab<LPR, NK>::LOADS / NK>(acc, slab_rsrc(slab, stride, splits), off, (int)stride, splits);
+  }
+#pragma unroll
+  for (int k = 0; k < KN; ++k) {
     int ch = sub + k * LPR;
     v[k][0] = v[k][1] = v[k][2] = v[k][3] = 0.f;
     if (rv && ch < nch) {
-      if (slab) {
-        // the producing GEMM left split-K fp32 slabs: sum them in slab order, add its bias, round to T as the
-        // separate reduce kernel would have stored it
-        f32x4 acc = *reinterpret_cast<const f32x4*>(slab_bias + 4 * ch);
-        for (int z = 0; z < splits; ++z)
-          acc += *reinterpret_cast<const f32x4*>(slab + ((int64_t)z * m + row) * c + 4 * ch);
-        unpack4<T>(pack4<T>(acc[0], acc[1], acc[2], acc[3]), v[k]);
-      } else {
-        unpack4<T>(*reinterpret_cast<const V4*>(x + row * c + 4 * ch), v[k]);
-      }
+      if constexpr (NK > 0) unpack4<T>(pack4<T>(acc[k][0], acc[k][1], acc[k][2], acc[k][3]), v[k]);
+      else unpack4<T>(*reinterpret_cast<const V4*>(x + row * c + 4 * ch), v[k]);
       s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
     }
   }
@@ -52,7 +68,7 @@ layernorm_kernel(const T* __restrict__ x, const float* __restrict__ gamma, const
   float mean = row_sum<LPR>(s) * inv_c;
   float q = 0.f;
 #pragma unroll
-  for (int k = 0; k < LN_MAXCH; ++k) {
+  for (int k = 0; k < KN; ++k) {
     int ch = sub + k * LPR;
     if (ch < nch) {
 #pragma unroll
@@ -62,7 +78,7 @@ layernorm_kernel(const T* __restrict__ x, const float* __restrict__ gamma, const
   float rstd = rsqrtf(row_sum<LPR>(q) * inv_c + eps);
   float s2 = 0.f;
 #pragma unroll
-  for (int k = 0; k < LN_MAXCH; ++k) {
+  for (int k = 0; k < KN; ++k) {
     int ch = sub + k * LPR;
     if (rv && ch < nch) {
       f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * ch);
@@ -83,7 +99,7 @@ layernorm_kernel(const T* __restrict__ x, const float* __restrict__ gamma, const
   mean = row_sum<LPR>(s2) * inv_c;
   q = 0.f;
 #pragma unroll
-  for (int k = 0; k < LN_MAXCH; ++k) {
+  for (int k = 0; k < KN; ++k) {
     int ch = sub + k * LPR;
     if (rv && ch < nch) {
 #pragma unroll
@@ -92,7 +108,7 @@ layernorm_kernel(const T* __restrict__ x, const float* __restrict__ gamma, const
   }
   rstd = rsqrtf(row_sum<LPR>(q) * inv_c + eps);
 #pragma unroll
-  for (int k = 0; k < LN_MAXCH; ++k) {
+  for (int k = 0; k < KN; ++k) {
     int ch = sub + k * LPR;
     if (rv && ch < nch) {
       f32x4 gm = *reinterpret_cast<const f32x4*>(gamma2 + 4 * ch);
@@ -138,23 +154,32 @@ static int launch_ln(const void* x, const float* gamma, const float* beta, const
   const int nch = c / 4;
   int lpr = 1;
   while (lpr < 64 && lpr < nch) lpr <<= 1;
-#define LN_LAUNCH(L)                                                                                     \
+#define LN_LAUNCH_NK(L, NK)                                                                              \
   {                                                                                                      \
     int64_t rows_per_block = 4 * (64 / L);                                                               \
-    hipLaunchKernelGGL((layernorm_kernel<T, L>), dim3((unsigned)cdiv(m, rows_per_block)), dim3(256), 0, s, \
+    hipLaunchKernelGGL((layernorm_kernel<T, L, NK>), dim3((unsigned)cdiv(m, rows_per_block)), dim3(256), 0, s, \
                        (const T*)x, gamma, beta, (const T*)res, (T*)y, gamma2, beta2, (T*)y2, m, c, eps, slab,   \
                        splits, slab_bias);                                                                \
   }
-  switch (lpr) {
-    case 1: LN_LAUNCH(1) break;
-    case 2: LN_LAUNCH(2) break;
-    case 4: LN_LAUNCH(4) break;
-    case 8: LN_LAUNCH(8) break;
-    case 16: LN_LAUNCH(16) break;
-    case 32: LN_LAUNCH(32) break;
-    default: LN_LAUNCH(64) break;
+#define LN_LAUNCH(L) \
+  if (slab) LN_LAUNCH_NK(L, 1) else LN_LAUNCH_NK(L, 0)
+  if (slab && nch > 64) {  // slab input with more than one chunk per lane
+    if (nch <= 128) LN_LAUNCH_NK(64, 2)
+    else if (nch <= 256) LN_LAUNCH_NK(64, 4)
+    else LN_LAUNCH_NK(64, 8)
+  } else {
+    switch (lpr) {
+      case 1: LN_LAUNCH(1) break;
+      case 2: LN_LAUNCH(2) break;
+      case 4: LN_LAUNCH(4) break;
+      case 8: LN_LAUNCH(8) break;
+      case 16: LN_LAUNCH(16) break;
+      case 32: LN_LAUNCH(32) break;
+      default: LN_LAUNCH(64) break;
+    }
   }
 #undef LN_LAUNCH
+#undef LN_LAUNCH_NK
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }
@@ -180,6 +205,8 @@ extern "C" int ptv3_layernorm_slabs(const float* slab, int splits, const float* 
                                     void* stream) {
   PTV3_REQUIRE(c > 0 && c % 4 == 0 && c <= 64 * LN_MAXCH * 4, "layernorm_slabs: c=%d must be a multiple of 4, <= 2048", c);
   PTV3_REQUIRE(slab && slab_bias && splits >= 1, "layernorm_slabs: slab, slab_bias and splits >= 1 are required");
+  PTV3_REQUIRE(m * c * splits * 4 < SLAB_MAX_BYTES, "layernorm_slabs: %d slabs of %lld x %d are 2 GiB or more", splits,
+               (long long)m, c);
   PTV3_REQUIRE((y2 == nullptr) || (gamma2 && beta2), "layernorm_slabs: y2 needs gamma2/beta2");
   PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "layernorm_slabs: bad dtype");
   if (m == 0) return PTV3_OK;

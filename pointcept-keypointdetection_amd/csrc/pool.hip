@@ -100,7 +100,14 @@ pool_assign_kernel(const int64_t* __restrict__ code0, const int64_t* __restrict_
   }
 }
 
-// LPR lanes per pooled row over the channel chunks; max over the members, then folded BN + act
+// LPR lanes per pooled row over the channel chunks; max over the members, then folded BN + act.
+// A member costs two dependent loads (order0[p], then its feature row): one member per iteration is two memory round
+// trips per member (DESIGN §0 rule 6).  The indices of PF_BATCH members are fetched together, then their rows, then the
+// maxima are taken in member order; a stride-2 cell has at most 8 members, so one batch of bf16 rows is the usual case
+// (fp32 rows are twice the registers: batches of 4 keep the kernel at 8 waves per SIMD).  Slots past the segment load
+// its last member and are not taken.
+template <typename T> struct PoolBatch { static constexpr int V = sizeof(T) == 2 ? 8 : 4; };
+
 template <typename T, int LPR>
 __global__ void __launch_bounds__(256)
 pool_feat_kernel(const T* __restrict__ feat, const int64_t* __restrict__ order0,
@@ -108,25 +115,40 @@ pool_feat_kernel(const T* __restrict__ feat, const int64_t* __restrict__ order0,
                  const float* __restrict__ bn_scale, const float* __restrict__ bn_shift, int act,
                  T* __restrict__ out) {
   typedef typename Vec4<T>::type V4;
-  constexpr int RPW = 64 / LPR;
+  constexpr int RPW = 64 / LPR, PF_BATCH = PoolBatch<T>::V;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane % LPR;
   const int64_t j = ((int64_t)blockIdx.x * 4 + wave) * RPW + lane / LPR;
   if (j >= n_out) return;
   const int s0 = seg_start[j], s1 = seg_start[j + 1];
+  const int last = s1 > 0 ? s1 - 1 : 0;
   const int nch = c / 4;
   for (int ch = sub; ch < nch; ch += LPR) {
+    f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
+    if (bn_scale) {
+      sc = *reinterpret_cast<const f32x4*>(bn_scale + 4 * ch);
+      sh = *reinterpret_cast<const f32x4*>(bn_shift + 4 * ch);
+    }
     float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    for (int p = s0; p < s1; ++p) {
-      float v[4];
-      unpack4<T>(*reinterpret_cast<const V4*>(feat + order0[p] * c + 4 * ch), v);
+    for (int p0 = s0; p0 < s1; p0 += PF_BATCH) {
+      int idx[PF_BATCH];   // point indices fit 31 bits (ptv3_pool_segments requires n < 2^31)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) mx[e] = fmaxf(mx[e], v[e]);
+      for (int u = 0; u < PF_BATCH; ++u) idx[u] = (int)order0[p0 + u < last ? p0 + u : last];
+      V4 row[PF_BATCH];
+#pragma unroll
+      for (int u = 0; u < PF_BATCH; ++u) row[u] = *reinterpret_cast<const V4*>(feat + (int64_t)idx[u] * c + 4 * ch);
+#pragma unroll
+      for (int u = 0; u < PF_BATCH; ++u) {
+        float v[4];
+        unpack4<T>(row[u], v);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) mx[e] = p0 + u < s1 ? fmaxf(mx[e], v[e]) : mx[e];
+      }
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float t = mx[e];
-      if (bn_scale) t = t * bn_scale[4 * ch + e] + bn_shift[4 * ch + e];
+      if (bn_scale) t = t * sc[e] + sh[e];
       if (act == PTV3_ACT_GELU) t = gelu_erf(t);
       else if (act == PTV3_ACT_RELU) t = fmaxf(t, 0.f);
       mx[e] = t;
