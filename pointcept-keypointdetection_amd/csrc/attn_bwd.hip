@@ -13,7 +13,7 @@
 #include <algorithm>
 #include "common.h"
 #include "profile.h"
-#include "../../include/ptv3_hip.h"
+#include "window_attn.h"   // the call description, its validator, and AB_MAX_TAB: one head's table column held in LDS
 
 namespace ptv3 {
 
@@ -32,8 +32,6 @@ struct AttnBwdArgs {
   unsigned drop_thr, drop_seed; float drop_scale;
   const float* lse_in;   // the forward's log2-domain log-sum-exp per (slot, head), or NULL: pass A recomputes it
 };
-
-constexpr int AB_MAX_TAB = 1024;  // 3 * (2 * pos_bnd + 1) entries of one head's table column held in LDS
 
 // bias of the pair (query coordinates qg, key coordinates kg) from one head's table column (already in the caller's
 // unit: natural for the gradient bins, x log2(e) for the softmax recompute)
@@ -452,59 +450,6 @@ extern "C" size_t ptv3_window_attn_bwd_workspace_bytes(int64_t n, int64_t n_pad,
          align256((size_t)n * sizeof(int32_t));
 }
 
-struct RpeBwd { const int32_t* grid; const float* table; int pos_bnd; float* dtable; };
-
-static int window_attn_bwd_impl(const void* qkv, const void* out, const void* dout, const int32_t* win_order,
-                                const int32_t* win_inverse, const int32_t* cu, int nwin, void* dqkv, int64_t n,
-                                int64_t n_pad, int c, int heads, int patch, float scale, int dtype, void* workspace,
-                                hipStream_t s, RpeBwd rpe = RpeBwd{nullptr, nullptr, 0, nullptr}, float p_drop = 0.f,
-                                unsigned seed = 0, const float* lse_in = nullptr) {
-  const int d = c / heads;
-  if (d != 16 && d != 32 && d != 64) {
-    set_error("window_attn_bwd: head_dim %d unsupported (16, 32, 64)", d);
-    return PTV3_ERR_UNSUPPORTED;
-  }
-  if (n == 0) return PTV3_OK;
-  const size_t esz = dtype == PTV3_F32 ? 4 : 2;
-  char* ws = (char*)workspace;
-  AttnBwdArgs a;
-  a.qkv = qkv; a.out = out; a.dout = dout; a.win_order = win_order; a.win_inverse = win_inverse;
-  a.dqkv_pad = ws; ws += align256((size_t)n_pad * 3 * c * esz);
-  a.lse = (float*)ws; ws += align256((size_t)n_pad * heads * sizeof(float));
-  a.delta = (float*)ws; ws += align256((size_t)n_pad * heads * sizeof(float));
-  int32_t* dup = (int32_t*)ws; ws += align256((size_t)n * sizeof(int32_t));
-  a.c = c; a.heads = heads; a.patch = patch; a.nwin = nwin; a.cu = cu;
-  a.grid = rpe.grid; a.table = rpe.table; a.pos_bnd = rpe.pos_bnd; a.dtab_slab = (float*)ws;
-  a.scale = scale; a.scale_log2e = scale * 1.44269504088896340736f;
-  a.drop_thr = p_drop > 0.f ? (unsigned)std::min(4294967295.0, (double)p_drop * 4294967296.0) : 0u;
-  a.drop_seed = seed; a.drop_scale = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
-  a.lse_in = lse_in;
-  if (hipMemsetAsync(dup, 0xFF, (size_t)n * sizeof(int32_t), s) != hipSuccess) return PTV3_ERR_LAUNCH;
-  hipLaunchKernelGGL(dup_slot_kernel, dim3((unsigned)cdiv(n_pad, 256)), dim3(256), 0, s, win_order, win_inverse, n_pad, dup);
-#define AB_CASE(T)                                     \
-  switch (d) {                                         \
-    case 16: launch_attn_bwd<T, 1>(a, s); break;       \
-    case 32: launch_attn_bwd<T, 2>(a, s); break;       \
-    default: launch_attn_bwd<T, 4>(a, s); break;       \
-  }
-  if (dtype == PTV3_F32) { AB_CASE(float) } else { AB_CASE(__bf16) }
-#undef AB_CASE
-  const int64_t tot = n * (3 * c / 4);
-  if (dtype == PTV3_F32)
-    hipLaunchKernelGGL(unpad_add_kernel<float>, dim3((unsigned)cdiv(tot, 256)), dim3(256), 0, s, (const float*)a.dqkv_pad,
-                       win_inverse, dup, n, 3 * c, (float*)dqkv);
-  else
-    hipLaunchKernelGGL(unpad_add_kernel<__bf16>, dim3((unsigned)cdiv(tot, 256)), dim3(256), 0, s,
-                       (const __bf16*)a.dqkv_pad, win_inverse, dup, n, 3 * c, (__bf16*)dqkv);
-  if (rpe.table) {
-    const int ncol = 3 * (2 * rpe.pos_bnd + 1);
-    hipLaunchKernelGGL(rpe_dtable_reduce_kernel, dim3((unsigned)cdiv((int64_t)ncol * heads, 256)), dim3(256), 0, s,
-                       a.dtab_slab, nwin, heads, (patch + 63) / 64, ncol, rpe.dtable);
-  }
-  PTV3_LAUNCH_CHECK();
-  return PTV3_OK;
-}
-
 extern "C" size_t ptv3_window_attn_rpe_bwd_workspace_bytes(int64_t n, int64_t n_pad, int c, int heads, int patch,
                                                            int pos_bnd, int dtype) {
   const int64_t blocks = (patch > 0 ? n_pad / patch : 0) * heads * ((patch + 63) / 64);
@@ -512,44 +457,82 @@ extern "C" size_t ptv3_window_attn_rpe_bwd_workspace_bytes(int64_t n, int64_t n_
          align256((size_t)blocks * 3 * (2 * pos_bnd + 1) * sizeof(float));
 }
 
+int ptv3::window_attn_backward(WindowAttnCall& w, const WindowAttnSpec& spec) {
+  bool empty;
+  const int ok = window_attn_validate(w, spec, true, &empty);
+  if (ok != PTV3_OK) return ok;
+  hipStream_t s = w.stream;
+  const int64_t n = w.n, n_pad = w.n_pad;
+  const int c = w.c, heads = w.heads;
+  if (empty) {   // no point, no gradient row; the table's gradient is still defined: zero
+    if (w.dtable && hipMemsetAsync(w.dtable, 0, (size_t)3 * (2 * w.pos_bnd + 1) * heads * sizeof(float), s) != hipSuccess)
+      return PTV3_ERR_LAUNCH;
+    return PTV3_OK;
+  }
+  const size_t esz = w.dtype == PTV3_F32 ? 4 : 2;
+  char* ws = (char*)w.workspace;
+  AttnBwdArgs a;
+  a.qkv = w.qkv; a.out = w.out; a.dout = w.dout; a.win_order = w.win_order; a.win_inverse = w.win_inverse;
+  a.dqkv_pad = ws; ws += align256((size_t)n_pad * 3 * c * esz);
+  a.lse = (float*)ws; ws += align256((size_t)n_pad * heads * sizeof(float));
+  a.delta = (float*)ws; ws += align256((size_t)n_pad * heads * sizeof(float));
+  int32_t* dup = (int32_t*)ws; ws += align256((size_t)n * sizeof(int32_t));
+  a.c = c; a.heads = heads; a.patch = w.patch; a.nwin = w.nwin; a.cu = w.cu_seqlens;
+  a.grid = w.grid_coord; a.table = w.rpe_table; a.pos_bnd = w.pos_bnd; a.dtab_slab = (float*)ws;
+  a.scale = w.scale; a.scale_log2e = w.scale * 1.44269504088896340736f;
+  a.drop_thr = w.p_drop > 0.f ? (unsigned)std::min(4294967295.0, (double)w.p_drop * 4294967296.0) : 0u;
+  a.drop_seed = w.seed; a.drop_scale = w.p_drop > 0.f ? 1.f / (1.f - w.p_drop) : 1.f;
+  a.lse_in = w.lse;
+  if (hipMemsetAsync(dup, 0xFF, (size_t)n * sizeof(int32_t), s) != hipSuccess) return PTV3_ERR_LAUNCH;
+  hipLaunchKernelGGL(dup_slot_kernel, dim3((unsigned)cdiv(n_pad, 256)), dim3(256), 0, s, w.win_order, w.win_inverse, n_pad, dup);
+  window_attn_dispatch(w.dtype, c / heads, [&](auto t, auto nd) {
+    launch_attn_bwd<typename decltype(t)::type, decltype(nd)::value>(a, s);
+    return (int)PTV3_OK;
+  });
+  const int64_t tot = n * (3 * c / 4);
+  if (w.dtype == PTV3_F32)
+    hipLaunchKernelGGL(unpad_add_kernel<float>, dim3((unsigned)cdiv(tot, 256)), dim3(256), 0, s, (const float*)a.dqkv_pad,
+                       w.win_inverse, dup, n, 3 * c, (float*)w.dqkv);
+  else
+    hipLaunchKernelGGL(unpad_add_kernel<__bf16>, dim3((unsigned)cdiv(tot, 256)), dim3(256), 0, s,
+                       (const __bf16*)a.dqkv_pad, w.win_inverse, dup, n, 3 * c, (__bf16*)w.dqkv);
+  if (w.rpe_table) {
+    const int ncol = 3 * (2 * w.pos_bnd + 1);
+    hipLaunchKernelGGL(rpe_dtable_reduce_kernel, dim3((unsigned)cdiv((int64_t)ncol * heads, 256)), dim3(256), 0, s,
+                       a.dtab_slab, w.nwin, heads, (w.patch + 63) / 64, ncol, w.dtable);
+  }
+  PTV3_LAUNCH_CHECK();
+  return PTV3_OK;
+}
+
+// the common arguments of the five backwards: the forward's call plus dout, dqkv and the workspace
+static WindowAttnCall bwd_call(const void* qkv, const void* out, const void* dout, const int32_t* win_order,
+                               const int32_t* win_inverse, void* dqkv, int64_t n, int64_t n_pad, int c, int heads,
+                               int patch, float scale, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  WindowAttnCall a = window_attn_call(qkv, win_order, win_inverse, const_cast<void*>(out), n, n_pad, c, heads, patch,
+                                      scale, dtype, stream);
+  a.dout = dout; a.dqkv = dqkv; a.workspace = workspace; a.workspace_bytes = workspace_bytes;
+  return a;
+}
+
 extern "C" int ptv3_window_attn_rpe_bwd(const void* qkv, const void* out, const void* dout, const int32_t* win_order,
                                         const int32_t* win_inverse, const int32_t* grid_coord, const float* rpe_table,
                                         int pos_bnd, void* dqkv, float* dtable, int64_t n, int64_t n_pad, int c,
                                         int heads, int patch, float scale, int dtype, void* workspace,
                                         size_t workspace_bytes, void* stream) {
-  PTV3_REQUIRE(heads > 0 && c % heads == 0, "window_attn_rpe_bwd: c=%d not divisible by heads=%d", c, heads);
-  PTV3_REQUIRE(patch >= 1 && patch <= 16384, "window_attn_rpe_bwd: patch %d outside [1,16384]", patch);
-  PTV3_REQUIRE(n_pad % patch == 0, "window_attn_rpe_bwd: n_pad=%lld is not a multiple of patch=%d", (long long)n_pad, patch);
-  PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "window_attn_rpe_bwd: bad dtype %d", dtype);
-  PTV3_REQUIRE(grid_coord && rpe_table && dtable && pos_bnd >= 0, "window_attn_rpe_bwd: grid_coord, rpe_table, dtable required");
-  if (3 * (2 * pos_bnd + 1) > AB_MAX_TAB) {
-    set_error("window_attn_rpe_bwd: table column of %d entries exceeds %d", 3 * (2 * pos_bnd + 1), AB_MAX_TAB);
-    return PTV3_ERR_UNSUPPORTED;
-  }
-  PTV3_REQUIRE(workspace_bytes >= ptv3_window_attn_rpe_bwd_workspace_bytes(n, n_pad, c, heads, patch, pos_bnd, dtype),
-               "window_attn_rpe_bwd: workspace too small");
-  if (n == 0) {
-    if (hipMemsetAsync(dtable, 0, (size_t)3 * (2 * pos_bnd + 1) * heads * sizeof(float), (hipStream_t)stream) != hipSuccess)
-      return PTV3_ERR_LAUNCH;
-    return PTV3_OK;
-  }
-  return window_attn_bwd_impl(qkv, out, dout, win_order, win_inverse, nullptr, (int)(n_pad / patch), dqkv, n, n_pad, c,
-                              heads, patch, scale, dtype, workspace, (hipStream_t)stream,
-                              RpeBwd{grid_coord, rpe_table, pos_bnd, dtable});
+  WindowAttnCall a = bwd_call(qkv, out, dout, win_order, win_inverse, dqkv, n, n_pad, c, heads, patch, scale, dtype,
+                              workspace, workspace_bytes, stream);
+  a.grid_coord = grid_coord; a.rpe_table = rpe_table; a.pos_bnd = pos_bnd; a.dtable = dtable;
+  return window_attn_backward(a, {"window_attn_rpe_bwd", WA_RAGGED_NO, false, /*rpe*/ true});
 }
 
 extern "C" int ptv3_window_attn_bwd(const void* qkv, const void* out, const void* dout, const int32_t* win_order,
                                     const int32_t* win_inverse, void* dqkv, int64_t n, int64_t n_pad, int c, int heads,
                                     int patch, float scale, int dtype, void* workspace, size_t workspace_bytes,
                                     void* stream) {
-  PTV3_REQUIRE(heads > 0 && c % heads == 0, "window_attn_bwd: c=%d not divisible by heads=%d", c, heads);
-  PTV3_REQUIRE(patch >= 1 && patch <= 16384, "window_attn_bwd: patch %d outside [1,16384]", patch);
-  PTV3_REQUIRE(n_pad % patch == 0, "window_attn_bwd: n_pad=%lld is not a multiple of patch=%d", (long long)n_pad, patch);
-  PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "window_attn_bwd: bad dtype %d", dtype);
-  PTV3_REQUIRE(workspace_bytes >= ptv3_window_attn_bwd_workspace_bytes(n, n_pad, c, heads, dtype),
-               "window_attn_bwd: workspace too small");
-  return window_attn_bwd_impl(qkv, out, dout, win_order, win_inverse, nullptr, (int)(n_pad / patch), dqkv, n, n_pad, c,
-                              heads, patch, scale, dtype, workspace, (hipStream_t)stream);
+  WindowAttnCall a = bwd_call(qkv, out, dout, win_order, win_inverse, dqkv, n, n_pad, c, heads, patch, scale, dtype,
+                              workspace, workspace_bytes, stream);
+  return window_attn_backward(a, {"window_attn_bwd", WA_RAGGED_NO});
 }
 
 extern "C" int ptv3_window_attn_varlen_bwd(const void* qkv, const void* out, const void* dout,
@@ -557,50 +540,28 @@ extern "C" int ptv3_window_attn_varlen_bwd(const void* qkv, const void* out, con
                                            const int32_t* cu_seqlens, int num_windows, void* dqkv, int64_t n,
                                            int64_t n_pad, int c, int heads, int max_seqlen, float scale, int dtype,
                                            void* workspace, size_t workspace_bytes, void* stream) {
-  PTV3_REQUIRE(heads > 0 && c % heads == 0, "window_attn_varlen_bwd: c=%d not divisible by heads=%d", c, heads);
-  PTV3_REQUIRE(max_seqlen >= 1 && max_seqlen <= 16384, "window_attn_varlen_bwd: max_seqlen %d outside [1,16384]", max_seqlen);
-  PTV3_REQUIRE(cu_seqlens != nullptr && num_windows >= 1, "window_attn_varlen_bwd: cu_seqlens with >= 1 window required");
-  PTV3_REQUIRE(n_pad <= (int64_t)num_windows * max_seqlen && n_pad >= num_windows,
-               "window_attn_varlen_bwd: n_pad=%lld cannot be split into %d windows of 1..%d slots", (long long)n_pad,
-               num_windows, max_seqlen);
-  PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "window_attn_varlen_bwd: bad dtype %d", dtype);
-  PTV3_REQUIRE(workspace_bytes >= ptv3_window_attn_bwd_workspace_bytes(n, n_pad, c, heads, dtype),
-               "window_attn_varlen_bwd: workspace too small");
-  return window_attn_bwd_impl(qkv, out, dout, win_order, win_inverse, cu_seqlens, num_windows, dqkv, n, n_pad, c, heads,
-                              max_seqlen, scale, dtype, workspace, (hipStream_t)stream);
+  WindowAttnCall a = bwd_call(qkv, out, dout, win_order, win_inverse, dqkv, n, n_pad, c, heads, max_seqlen, scale, dtype,
+                              workspace, workspace_bytes, stream);
+  a.cu_seqlens = cu_seqlens; a.num_windows = num_windows;
+  return window_attn_backward(a, {"window_attn_varlen_bwd", WA_RAGGED_REQUIRED});
 }
 
 extern "C" int ptv3_window_attn_drop_bwd(const void* qkv, const void* out, const void* dout, const int32_t* win_order,
                                          const int32_t* win_inverse, const int32_t* cu_seqlens, int num_windows, void* dqkv,
                                          int64_t n, int64_t n_pad, int c, int heads, int patch, float scale, float p_drop,
                                          uint32_t seed, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  PTV3_REQUIRE(heads > 0 && c % heads == 0, "window_attn_drop_bwd: c=%d not divisible by heads=%d", c, heads);
-  PTV3_REQUIRE(patch >= 1 && patch <= 16384, "window_attn_drop_bwd: patch %d outside [1,16384]", patch);
-  PTV3_REQUIRE(cu_seqlens != nullptr || n_pad % patch == 0, "window_attn_drop_bwd: n_pad=%lld is not a multiple of patch=%d",
-               (long long)n_pad, patch);
-  PTV3_REQUIRE(p_drop > 0.f && p_drop < 1.f, "window_attn_drop_bwd: p_drop %g outside (0,1)", (double)p_drop);
-  PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "window_attn_drop_bwd: bad dtype %d", dtype);
-  PTV3_REQUIRE(workspace_bytes >= ptv3_window_attn_bwd_workspace_bytes(n, n_pad, c, heads, dtype),
-               "window_attn_drop_bwd: workspace too small");
-  const int nwin = cu_seqlens ? num_windows : (int)(n_pad / patch);
-  return window_attn_bwd_impl(qkv, out, dout, win_order, win_inverse, cu_seqlens, nwin, dqkv, n, n_pad, c, heads, patch,
-                              scale, dtype, workspace, (hipStream_t)stream, RpeBwd{nullptr, nullptr, 0, nullptr}, p_drop, seed);
+  WindowAttnCall a = bwd_call(qkv, out, dout, win_order, win_inverse, dqkv, n, n_pad, c, heads, patch, scale, dtype,
+                              workspace, workspace_bytes, stream);
+  a.cu_seqlens = cu_seqlens; a.num_windows = num_windows; a.p_drop = p_drop; a.seed = seed;
+  return window_attn_backward(a, {"window_attn_drop_bwd", WA_RAGGED_OPTIONAL, false, false, /*drop*/ true});
 }
 
 extern "C" int ptv3_window_attn_train_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
                                           const int32_t* win_order, const int32_t* win_inverse, const int32_t* cu_seqlens,
                                           int num_windows, void* dqkv, int64_t n, int64_t n_pad, int c, int heads, int patch,
                                           float scale, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-  PTV3_REQUIRE(heads > 0 && c % heads == 0, "window_attn_train_bwd: c=%d not divisible by heads=%d", c, heads);
-  PTV3_REQUIRE(patch >= 1 && patch <= 16384, "window_attn_train_bwd: patch %d outside [1,16384]", patch);
-  PTV3_REQUIRE(cu_seqlens != nullptr || n_pad % patch == 0, "window_attn_train_bwd: n_pad=%lld is not a multiple of patch=%d",
-               (long long)n_pad, patch);
-  PTV3_REQUIRE(lse != nullptr, "window_attn_train_bwd: the forward's lse is required");
-  PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "window_attn_train_bwd: bad dtype %d", dtype);
-  PTV3_REQUIRE(workspace_bytes >= ptv3_window_attn_bwd_workspace_bytes(n, n_pad, c, heads, dtype),
-               "window_attn_train_bwd: workspace too small");
-  const int nwin = cu_seqlens ? num_windows : (int)(n_pad / patch);
-  return window_attn_bwd_impl(qkv, out, dout, win_order, win_inverse, cu_seqlens, nwin, dqkv, n, n_pad, c, heads, patch,
-                              scale, dtype, workspace, (hipStream_t)stream, RpeBwd{nullptr, nullptr, 0, nullptr}, 0.f, 0,
-                              lse);
+  WindowAttnCall a = bwd_call(qkv, out, dout, win_order, win_inverse, dqkv, n, n_pad, c, heads, patch, scale, dtype,
+                              workspace, workspace_bytes, stream);
+  a.cu_seqlens = cu_seqlens; a.num_windows = num_windows; a.lse = const_cast<float*>(lse);
+  return window_attn_backward(a, {"window_attn_train_bwd", WA_RAGGED_OPTIONAL, /*lse*/ true});
 }

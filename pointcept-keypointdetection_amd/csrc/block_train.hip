@@ -10,7 +10,7 @@
 //   f2 = f1 + mask1 * proj(attn(qkv(LN1(f1))))
 //   out = f2 + mask2 * fc2(GELU(fc1(LN2(f2))))
 #include "common.h"
-#include "../../include/ptv3_hip.h"
+#include "window_attn.h"
 
 namespace ptv3 {
 
@@ -105,6 +105,14 @@ static int check_block(const ptv3_block_train* b, const char* what) {
   return PTV3_OK;
 }
 
+// the block's attention, forward or backward: uniform or ragged windows, with or without the stored log-sum-exp rows
+static WindowAttnCall block_attn_call(const ptv3_block_train* b, hipStream_t s) {
+  WindowAttnCall a = window_attn_call(b->qkv, b->win_order, b->win_inverse, b->a, b->n, b->n_pad, b->c, b->heads, b->patch,
+                                      b->scale, b->dtype, s);
+  a.cu_seqlens = b->cu_seqlens; a.num_windows = b->num_windows; a.sum_len_sq = b->sum_len_sq; a.lse = b->attn_lse;
+  return a;
+}
+
 }  // namespace ptv3
 
 using namespace ptv3;
@@ -150,15 +158,8 @@ extern "C" int ptv3_block_train_fwd(const ptv3_block_train* b, void* stream) {
   TRY(ptv3_layernorm(b->c2, b->g0, b->b0, b->feat, b->f1, b->g1, b->b1, b->t3, n, c, b->eps, dt, s));
   TRY(ptv3_gemm(b->t3, b->w_qkv, b->qkv, n, c, 3 * c, 1, nullptr, nullptr, b->b_qkv, nullptr, nullptr, PTV3_ACT_NONE,
                 nullptr, nullptr, nullptr, dt, scratch, sb, s));
-  if (b->attn_lse)     // the backward takes the log-sum-exp rows from here instead of recomputing them
-    TRY(ptv3_window_attn_train_fwd(b->qkv, b->win_order, b->win_inverse, b->cu_seqlens, b->num_windows, b->a, b->attn_lse,
-                                   n, b->n_pad, c, b->heads, b->patch, b->scale, b->sum_len_sq, dt, s));
-  else if (b->cu_seqlens)
-    TRY(ptv3_window_attn_varlen_fwd(b->qkv, b->win_order, b->win_inverse, b->cu_seqlens, b->num_windows, b->a, n,
-                                    b->n_pad, c, b->heads, b->patch, b->scale, b->sum_len_sq, dt, s));
-  else
-    TRY(ptv3_window_attn_fwd(b->qkv, b->win_order, b->win_inverse, b->a, n, b->n_pad, c, b->heads, b->patch, b->scale,
-                             nullptr, dt, s));
+  WindowAttnCall at = block_attn_call(b, s);   // with attn_lse the backward takes the log-sum-exp rows from here
+  TRY(window_attn_forward(at, {"window_attn", WA_RAGGED_OPTIONAL}));
   if (b->mask1) {
     TRY(ptv3_gemm(b->a, b->w_proj, tmp, n, c, c, 1, nullptr, nullptr, b->b_proj, nullptr, nullptr, PTV3_ACT_NONE,
                   nullptr, nullptr, nullptr, dt, scratch, sb, s));
@@ -255,15 +256,9 @@ extern "C" int ptv3_block_train_bwd(const ptv3_block_train* b, void* stream) {
   if (b->mask1) { TRY(rowscale_add(df2, b->mask1, b->keep1, nullptr, dp, n, c, dt, s)); dpp = dp; }
   GEMM(dpp, b->wt_proj, da, c, c);
   GEMM_TN(dpp, b->a, b->dw_proj, b->db_proj, c, c);
-  if (b->attn_lse)
-    TRY(ptv3_window_attn_train_bwd(b->qkv, b->a, da, b->attn_lse, b->win_order, b->win_inverse, b->cu_seqlens,
-                                   b->num_windows, dqkv, n, b->n_pad, c, b->heads, b->patch, b->scale, dt, scratch, sb, s));
-  else if (b->cu_seqlens)
-    TRY(ptv3_window_attn_varlen_bwd(b->qkv, b->a, da, b->win_order, b->win_inverse, b->cu_seqlens, b->num_windows, dqkv,
-                                    n, b->n_pad, c, b->heads, b->patch, b->scale, dt, scratch, sb, s));
-  else
-    TRY(ptv3_window_attn_bwd(b->qkv, b->a, da, b->win_order, b->win_inverse, dqkv, n, b->n_pad, c, b->heads, b->patch,
-                             b->scale, dt, scratch, sb, s));
+  WindowAttnCall at = block_attn_call(b, s);
+  at.dout = da; at.dqkv = dqkv; at.workspace = scratch; at.workspace_bytes = sb;
+  TRY(window_attn_backward(at, {"window_attn_bwd", WA_RAGGED_OPTIONAL}));
   GEMM(dqkv, b->wt_qkv, dt3, 3 * c, c);
   GEMM_TN(dqkv, b->t3, b->dw_qkv, b->db_qkv, 3 * c, c);
   // df1: the block's gradient with respect to feat when the conv reads another tensor, an intermediate otherwise

@@ -18,7 +18,7 @@
 #include <stdlib.h>
 #include <vector>
 #include "common.h"
-#include "../../include/ptv3_hip.h"
+#include "window_attn.h"
 
 namespace ptv3 {
 
@@ -299,11 +299,9 @@ struct Run {
   // SerializedAttention core (:184-216): uniform K-slot windows, or ragged ones (a scene shorter than the fixed patch
   // of enable_flash=True is one short window, :131-133 + the varlen call :207-215)
   void attention(const Level& L, const Plan& P, const void* qkv, void* out, int C, int H, int oi, float scale) {
-    if (P.cu)
-      RUN(ptv3_window_attn_varlen_fwd(qkv, P.wo[oi], P.wi[oi], P.cu, P.nwin, out, L.n, P.n_pad, C, H, P.K, scale,
-                                      P.sum_len_sq, d->dtype, sf));
-    else
-      RUN(ptv3_window_attn_fwd(qkv, P.wo[oi], P.wi[oi], out, L.n, P.n_pad, C, H, P.K, scale, nullptr, d->dtype, sf));
+    WindowAttnCall a = window_attn_call(qkv, P.wo[oi], P.wi[oi], out, L.n, P.n_pad, C, H, P.K, scale, d->dtype, sf);
+    a.cu_seqlens = P.cu; a.num_windows = P.nwin; a.sum_len_sq = P.sum_len_sq;
+    RUN(window_attn_forward(a, {"window_attn", WA_RAGGED_OPTIONAL}));
   }
 
   // Block.forward (:318-338), eval, pre_norm; cpe Linear folded into the conv taps

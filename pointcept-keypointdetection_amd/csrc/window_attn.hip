@@ -10,7 +10,7 @@
 #include "common.h"
 #include <stdlib.h>
 #include "profile.h"
-#include "../../include/ptv3_hip.h"
+#include "window_attn.h"
 
 namespace ptv3 {
 
@@ -601,15 +601,17 @@ static void full_config(int64_t pairs, int K, int qt_max, size_t lds, int* waves
   *qt_out = bq;
 }
 
-static bool g_last_launch_tiled = false;   // which kernel the last launch_window_attn chose (profiling tag only)
-
+// The resident-window kernel when the window fits LDS, the tiled kernel otherwise.  Attention dropout always takes the
+// tiled kernel (the mask costs ~12 integer operations per score; the resident-window kernel stays free of it); the RPE
+// table lookup exists in the resident-window kernel only.  a.tiled tells the caller which one ran.
 template <typename T, int ND>
-static int launch_window_attn(const void* qkv, const int32_t* wo, const int32_t* wi, void* out, int C, int H,
-                              int K, int nwin, float scale, const float* rpe, hipStream_t s,
-                              RpeTable rt = RpeTable{nullptr, nullptr, 0}, const int32_t* cu = nullptr,
-                              float* lse = nullptr) {
+static int launch_window_attn(WindowAttnCall& a) {
   constexpr int D = 16 * ND;
   constexpr int QT = WaCfg<T, ND>::QT;
+  const int C = a.c, H = a.heads, K = a.patch, nwin = a.nwin;
+  const float scale_log2e = a.scale * 1.44269504088896340736f;
+  const RpeTable rt{a.grid_coord, a.rpe_table, a.pos_bnd};
+  const bool drop = a.p_drop > 0.f;
   const int Kpad = (K + WA_KT - 1) / WA_KT * WA_KT;
   size_t lds_full = ((size_t)Kpad * (D + 4) + (size_t)D * (Kpad + WaFull<T>::VPAD)) * sizeof(T) + (size_t)Kpad * 4;
   if (rt.table) lds_full += (size_t)Kpad * 12 + (size_t)3 * (2 * rt.pos_bnd + 1) * 4;
@@ -617,17 +619,17 @@ static int launch_window_attn(const void* qkv, const int32_t* wo, const int32_t*
     set_error("window_attn_rpe: window of %d keys does not fit the resident-window kernel", K);
     return PTV3_ERR_UNSUPPORTED;
   }
-  g_last_launch_tiled = lds_full > 160 * 1024;
-  if (lds_full <= 160 * 1024) {
+  a.tiled = drop || lds_full > 160 * 1024;
+  if (!a.tiled) {
     int waves, qt;
     full_config(nwin * (int64_t)H, K, WaCfg<T, ND>::QT, lds_full, &waves, &qt);
-    const FullArgs<T> a{(const T*)qkv, wo, wi, (T*)out, C, H, K, Kpad, nwin, scale * 1.44269504088896340736f, rpe,
-                        rt, waves, lds_full, s, cu, lse};
-    const int rpe_mode = rt.table ? 2 : (rpe ? 1 : 0);
+    const FullArgs<T> fa{(const T*)a.qkv, a.win_order, a.win_inverse, (T*)a.out, C, H, K, Kpad, nwin, scale_log2e,
+                         a.rpe_bias, rt, waves, lds_full, a.stream, a.cu_seqlens, a.lse};
+    const int rpe_mode = rt.table ? 2 : (a.rpe_bias ? 1 : 0);
     constexpr int QTMAX = WaCfg<T, ND>::QT;
-    if (qt >= 4 && QTMAX >= 4) launch_full_rpe<T, ND, (QTMAX >= 4 ? 4 : QTMAX)>(a, rpe_mode);
-    else if (qt >= 2 && QTMAX >= 2) launch_full_rpe<T, ND, (QTMAX >= 2 ? 2 : QTMAX)>(a, rpe_mode);
-    else launch_full_rpe<T, ND, 1>(a, rpe_mode);
+    if (qt >= 4 && QTMAX >= 4) launch_full_rpe<T, ND, (QTMAX >= 4 ? 4 : QTMAX)>(fa, rpe_mode);
+    else if (qt >= 2 && QTMAX >= 2) launch_full_rpe<T, ND, (QTMAX >= 2 ? 2 : QTMAX)>(fa, rpe_mode);
+    else launch_full_rpe<T, ND, 1>(fa, rpe_mode);
     PTV3_LAUNCH_CHECK();
     return PTV3_OK;
   }
@@ -636,179 +638,123 @@ static int launch_window_attn(const void* qkv, const int32_t* wo, const int32_t*
   const size_t lds = (size_t)(WA_KT * (D + 4) + D * (WA_KT + 4)) * sizeof(T) + (size_t)K * 4;
   if (lds > 64 * 1024) ensure_dynamic_lds(reinterpret_cast<const void*>(&window_attn_kernel<T, ND>), 160 * 1024);
   const unsigned nwg = (unsigned)nwin * H * qsplit;
-  hipLaunchKernelGGL((window_attn_kernel<T, ND>), dim3(nwg), dim3(WA_THREADS), lds, s, (const T*)qkv, wo, wi,
-                     (T*)out, C, H, K, nwin, qsplit, scale * 1.44269504088896340736f, rpe, cu, 0u, 0u, 1.f, lse);
+  const unsigned thr = drop ? (unsigned)std::min(4294967295.0, (double)a.p_drop * 4294967296.0) : 0u;
+  hipLaunchKernelGGL((window_attn_kernel<T, ND>), dim3(nwg), dim3(WA_THREADS), lds, a.stream, (const T*)a.qkv,
+                     a.win_order, a.win_inverse, (T*)a.out, C, H, K, nwin, qsplit, scale_log2e, a.rpe_bias, a.cu_seqlens,
+                     thr, drop ? a.seed : 0u, drop ? 1.f / (1.f - a.p_drop) : 1.f, a.lse);
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }
 
-// training forward with attention dropout: always the tiled kernel (the mask costs ~12 integer operations per score; the
-// resident-window kernel stays free of it)
-template <typename T, int ND>
-static int launch_window_attn_drop(const void* qkv, const int32_t* wo, const int32_t* wi, void* out, int C, int H, int K,
-                                   int nwin, float scale, const int32_t* cu, unsigned thr, unsigned seed, float dscale,
-                                   hipStream_t s) {
-  constexpr int D = 16 * ND;
-  constexpr int QT = WaCfg<T, ND>::QT;
-  constexpr int QB = WA_WAVES * QT * 16;
-  const int qsplit = (K + QB - 1) / QB;
-  const size_t lds = (size_t)(WA_KT * (D + 4) + D * (WA_KT + 4)) * sizeof(T) + (size_t)K * 4;
-  if (lds > 64 * 1024) ensure_dynamic_lds(reinterpret_cast<const void*>(&window_attn_kernel<T, ND>), 160 * 1024);
-  const unsigned nwg = (unsigned)nwin * H * qsplit;
-  hipLaunchKernelGGL((window_attn_kernel<T, ND>), dim3(nwg), dim3(WA_THREADS), lds, s, (const T*)qkv, wo, wi, (T*)out, C, H,
-                     K, nwin, qsplit, scale * 1.44269504088896340736f, (const float*)nullptr, cu, thr, seed, dscale);
-  PTV3_LAUNCH_CHECK();
+int window_attn_validate(WindowAttnCall& a, const WindowAttnSpec& spec, bool backward, bool* empty) {
+  const char* nm = spec.name;
+  PTV3_REQUIRE(a.heads > 0 && a.c % a.heads == 0, "%s: c=%d not divisible by heads=%d", nm, a.c, a.heads);
+  PTV3_REQUIRE(a.patch >= 1 && a.patch <= 16384, "%s: %s %d outside [1,16384]", nm,
+               spec.ragged == WA_RAGGED_REQUIRED ? "max_seqlen" : "patch", a.patch);
+  if (spec.ragged == WA_RAGGED_NO) a.cu_seqlens = nullptr;
+  if (spec.ragged == WA_RAGGED_REQUIRED) {
+    PTV3_REQUIRE(a.cu_seqlens != nullptr && a.num_windows >= 1, "%s: cu_seqlens with >= 1 window required", nm);
+    PTV3_REQUIRE(a.n_pad <= (int64_t)a.num_windows * a.patch && a.n_pad >= a.num_windows,
+                 "%s: n_pad=%lld cannot be split into %d windows of 1..%d slots", nm, (long long)a.n_pad, a.num_windows,
+                 a.patch);
+  } else {
+    PTV3_REQUIRE(a.cu_seqlens != nullptr || a.n_pad % a.patch == 0, "%s: n_pad=%lld is not a multiple of patch=%d%s", nm,
+                 (long long)a.n_pad, a.patch, spec.ragged == WA_RAGGED_NO ? " (this entry takes uniform windows only)" : "");
+  }
+  PTV3_REQUIRE(a.p_drop == 0.f ? !spec.drop : (a.p_drop > 0.f && a.p_drop < 1.f), "%s: p_drop %g outside (0,1)", nm,
+               (double)a.p_drop);
+  PTV3_REQUIRE(!spec.lse || a.lse != nullptr, "%s: lse (n_pad x heads floats) is required", nm);
+  PTV3_REQUIRE(a.dtype == PTV3_F32 || a.dtype == PTV3_BF16, "%s: bad dtype %d", nm, a.dtype);
+  if (spec.rpe) {
+    PTV3_REQUIRE(a.grid_coord && a.rpe_table && a.pos_bnd >= 0, "%s: grid_coord, rpe_table and pos_bnd >= 0 are required", nm);
+    if (!backward) PTV3_REQUIRE(a.pos_bnd <= 4096, "%s: pos_bnd %d outside [0,4096]", nm, a.pos_bnd);
+    if (backward) PTV3_REQUIRE(a.dtable != nullptr, "%s: dtable is required", nm);
+    if (backward && 3 * (2 * a.pos_bnd + 1) > AB_MAX_TAB) {
+      set_error("%s: table column of %d entries exceeds %d", nm, 3 * (2 * a.pos_bnd + 1), AB_MAX_TAB);
+      return PTV3_ERR_UNSUPPORTED;
+    }
+  }
+  if (backward) {
+    const size_t need = a.rpe_table
+        ? ptv3_window_attn_rpe_bwd_workspace_bytes(a.n, a.n_pad, a.c, a.heads, a.patch, a.pos_bnd, a.dtype)
+        : ptv3_window_attn_bwd_workspace_bytes(a.n, a.n_pad, a.c, a.heads, a.dtype);
+    PTV3_REQUIRE(a.workspace_bytes >= need, "%s: workspace too small", nm);
+  }
+  a.nwin = a.cu_seqlens ? a.num_windows : (int)(a.n_pad / a.patch);
+  *empty = a.n == 0;
+  if (*empty && (!backward || spec.rpe)) return PTV3_OK;
+  const int d = a.c / a.heads;
+  if (d != 16 && d != 32 && d != 64) {
+    set_error("%s: head_dim %d unsupported (16, 32, 64)", nm, d);
+    return PTV3_ERR_UNSUPPORTED;
+  }
   return PTV3_OK;
+}
+
+int window_attn_forward(WindowAttnCall& a, const WindowAttnSpec& spec) {
+  bool empty;
+  const int ok = window_attn_validate(a, spec, false, &empty);
+  if (ok != PTV3_OK || empty) return ok;
+  const int esz = a.dtype == PTV3_F32 ? 4 : 2;
+  // algorithmic work: 4 * sum_w len_w^2 * c flops; qkv read + out write + the two index maps (+ the
+  // voxel coordinates of the RPE table lookup)
+  const double len_sq = a.cu_seqlens && a.sum_len_sq > 0 ? a.sum_len_sq : (double)a.n_pad * a.patch;
+  const double bytes = (double)a.n_pad * 3 * a.c * esz + (double)a.n * a.c * esz + 4.0 * (a.n_pad + a.n);
+  const int prof = prof_begin(a.stream, PROF_WINDOW_ATTN, 4.0 * len_sq * a.c, a.rpe_table ? bytes + 12.0 * a.n_pad : bytes,
+                              nullptr, 0, 0.0);
+  const int rc = window_attn_dispatch(a.dtype, a.c / a.heads, [&](auto t, auto nd) {
+    return launch_window_attn<typename decltype(t)::type, decltype(nd)::value>(a);
+  });
+  prof_kernel(prof, a.tiled ? PK_ATTN_TILED : PK_ATTN_FULL);
+  prof_end(prof, a.stream);
+  return rc;
 }
 
 }  // namespace ptv3
 
 using namespace ptv3;
 
-extern "C" int ptv3_window_attn_drop_fwd(const void* qkv, const int32_t* win_order, const int32_t* win_inverse,
-                                         const int32_t* cu_seqlens, int num_windows, void* out, int64_t n, int64_t n_pad,
-                                         int c, int heads, int patch, float scale, float p_drop, uint32_t seed, int dtype,
-                                         void* stream) {
-  PTV3_REQUIRE(heads > 0 && c % heads == 0, "window_attn_drop: c=%d not divisible by heads=%d", c, heads);
-  PTV3_REQUIRE(patch >= 1 && patch <= 16384, "window_attn_drop: patch %d outside [1,16384]", patch);
-  PTV3_REQUIRE(cu_seqlens != nullptr || n_pad % patch == 0, "window_attn_drop: n_pad=%lld is not a multiple of patch=%d",
-               (long long)n_pad, patch);
-  PTV3_REQUIRE(p_drop > 0.f && p_drop < 1.f, "window_attn_drop: p_drop %g outside (0,1)", (double)p_drop);
-  PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "window_attn_drop: bad dtype %d", dtype);
-  const int d = c / heads;
-  if (n == 0) return PTV3_OK;
-  if (d != 16 && d != 32 && d != 64) {
-    set_error("window_attn_drop: head_dim %d unsupported (16, 32, 64)", d);
-    return PTV3_ERR_UNSUPPORTED;
-  }
-  const int nwin = cu_seqlens ? num_windows : (int)(n_pad / patch);
-  const unsigned thr = (unsigned)std::min(4294967295.0, (double)p_drop * 4294967296.0);
-  const float dscale = 1.f / (1.f - p_drop);
-  hipStream_t s = (hipStream_t)stream;
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
-  const int prof = prof_begin(s, PROF_WINDOW_ATTN, 4.0 * n_pad * patch * c,
-                              (double)n_pad * 3 * c * esz + (double)n * c * esz + 4.0 * (n_pad + n), nullptr, 0, 0.0);
-  prof_kernel(prof, PK_ATTN_TILED);
-  int rc = PTV3_ERR_UNSUPPORTED;
-#define WAD_CASE(T)                                                                                                       \
-  switch (d) {                                                                                                            \
-    case 16: rc = launch_window_attn_drop<T, 1>(qkv, win_order, win_inverse, out, c, heads, patch, nwin, scale, cu_seqlens, thr, seed, dscale, s); break; \
-    case 32: rc = launch_window_attn_drop<T, 2>(qkv, win_order, win_inverse, out, c, heads, patch, nwin, scale, cu_seqlens, thr, seed, dscale, s); break; \
-    default: rc = launch_window_attn_drop<T, 4>(qkv, win_order, win_inverse, out, c, heads, patch, nwin, scale, cu_seqlens, thr, seed, dscale, s); break; \
-  }
-  if (dtype == PTV3_F32) { WAD_CASE(float) } else { WAD_CASE(__bf16) }
-#undef WAD_CASE
-  prof_end(prof, s);
-  return rc;
-}
-
-static int window_attn_fwd_impl(const void* qkv, const int32_t* win_order, const int32_t* win_inverse,
-                                const int32_t* cu, int nwin, void* out, int64_t n, int64_t n_pad, int c, int heads,
-                                int patch, float scale, const float* rpe_bias, int dtype, double flops, hipStream_t s,
-                                float* lse = nullptr) {
-  const int d = c / heads;
-  if (n == 0) return PTV3_OK;
-  if (d != 16 && d != 32 && d != 64) {
-    set_error("window_attn: head_dim %d unsupported (16, 32, 64)", d);
-    return PTV3_ERR_UNSUPPORTED;
-  }
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
-  // algorithmic work: 4 * sum_w len_w^2 * c flops; qkv read + out write + the two index maps
-  const int prof = prof_begin(s, PROF_WINDOW_ATTN, flops,
-                              (double)n_pad * 3 * c * esz + (double)n * c * esz + 4.0 * (n_pad + n), nullptr, 0, 0.0);
-  int rc = PTV3_ERR_UNSUPPORTED;
-  const RpeTable none{nullptr, nullptr, 0};
-#define WA_CASE(T)                                                                                          \
-  switch (d) {                                                                                              \
-    case 16: rc = launch_window_attn<T, 1>(qkv, win_order, win_inverse, out, c, heads, patch, nwin, scale, rpe_bias, s, none, cu, lse); break; \
-    case 32: rc = launch_window_attn<T, 2>(qkv, win_order, win_inverse, out, c, heads, patch, nwin, scale, rpe_bias, s, none, cu, lse); break; \
-    case 64: rc = launch_window_attn<T, 4>(qkv, win_order, win_inverse, out, c, heads, patch, nwin, scale, rpe_bias, s, none, cu, lse); break; \
-    default: break;                                                                                         \
-  }
-  if (dtype == PTV3_F32) { WA_CASE(float) } else { WA_CASE(__bf16) }
-#undef WA_CASE
-  prof_kernel(prof, g_last_launch_tiled ? PK_ATTN_TILED : PK_ATTN_FULL);
-  prof_end(prof, s);
-  return rc;
-}
-
 extern "C" int ptv3_window_attn_fwd(const void* qkv, const int32_t* win_order, const int32_t* win_inverse,
                                     void* out, int64_t n, int64_t n_pad, int c, int heads, int patch,
                                     float scale, const float* rpe_bias, int dtype, void* stream) {
-  PTV3_REQUIRE(heads > 0 && c % heads == 0, "window_attn: c=%d not divisible by heads=%d", c, heads);
-  PTV3_REQUIRE(patch >= 1 && patch <= 16384, "window_attn: patch %d outside [1,16384]", patch);
-  PTV3_REQUIRE(n_pad % patch == 0, "window_attn: n_pad=%lld is not a multiple of patch=%d (ragged windows: "
-               "ptv3_window_attn_varlen_fwd)", (long long)n_pad, patch);
-  PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "window_attn: bad dtype %d", dtype);
-  return window_attn_fwd_impl(qkv, win_order, win_inverse, nullptr, (int)(n_pad / patch), out, n, n_pad, c, heads,
-                              patch, scale, rpe_bias, dtype, 4.0 * n_pad * patch * c, (hipStream_t)stream);
+  WindowAttnCall a = window_attn_call(qkv, win_order, win_inverse, out, n, n_pad, c, heads, patch, scale, dtype, stream);
+  a.rpe_bias = rpe_bias;
+  return window_attn_forward(a, {"window_attn", WA_RAGGED_NO});
 }
 
 extern "C" int ptv3_window_attn_varlen_fwd(const void* qkv, const int32_t* win_order, const int32_t* win_inverse,
                                            const int32_t* cu_seqlens, int num_windows, void* out, int64_t n,
                                            int64_t n_pad, int c, int heads, int max_seqlen, float scale,
                                            double sum_len_sq, int dtype, void* stream) {
-  PTV3_REQUIRE(heads > 0 && c % heads == 0, "window_attn_varlen: c=%d not divisible by heads=%d", c, heads);
-  PTV3_REQUIRE(max_seqlen >= 1 && max_seqlen <= 16384, "window_attn_varlen: max_seqlen %d outside [1,16384]", max_seqlen);
-  PTV3_REQUIRE(cu_seqlens != nullptr && num_windows >= 1, "window_attn_varlen: cu_seqlens with >= 1 window required");
-  PTV3_REQUIRE(n_pad <= (int64_t)num_windows * max_seqlen && n_pad >= num_windows,
-               "window_attn_varlen: n_pad=%lld cannot be split into %d windows of 1..%d slots", (long long)n_pad,
-               num_windows, max_seqlen);
-  PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "window_attn_varlen: bad dtype %d", dtype);
-  const double flops = 4.0 * (sum_len_sq > 0 ? sum_len_sq : (double)n_pad * max_seqlen) * c;
-  return window_attn_fwd_impl(qkv, win_order, win_inverse, cu_seqlens, num_windows, out, n, n_pad, c, heads,
-                              max_seqlen, scale, nullptr, dtype, flops, (hipStream_t)stream);
+  WindowAttnCall a = window_attn_call(qkv, win_order, win_inverse, out, n, n_pad, c, heads, max_seqlen, scale, dtype, stream);
+  a.cu_seqlens = cu_seqlens; a.num_windows = num_windows; a.sum_len_sq = sum_len_sq;
+  return window_attn_forward(a, {"window_attn_varlen", WA_RAGGED_REQUIRED});
 }
 
 extern "C" int ptv3_window_attn_train_fwd(const void* qkv, const int32_t* win_order, const int32_t* win_inverse,
                                           const int32_t* cu_seqlens, int num_windows, void* out, float* lse, int64_t n,
                                           int64_t n_pad, int c, int heads, int patch, float scale, double sum_len_sq,
                                           int dtype, void* stream) {
-  PTV3_REQUIRE(heads > 0 && c % heads == 0, "window_attn_train: c=%d not divisible by heads=%d", c, heads);
-  PTV3_REQUIRE(patch >= 1 && patch <= 16384, "window_attn_train: patch %d outside [1,16384]", patch);
-  PTV3_REQUIRE(cu_seqlens != nullptr || n_pad % patch == 0, "window_attn_train: n_pad=%lld is not a multiple of patch=%d",
-               (long long)n_pad, patch);
-  PTV3_REQUIRE(lse != nullptr, "window_attn_train: lse (n_pad x heads floats) is required");
-  PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "window_attn_train: bad dtype %d", dtype);
-  const int nwin = cu_seqlens ? num_windows : (int)(n_pad / patch);
-  const double flops = 4.0 * (cu_seqlens && sum_len_sq > 0 ? sum_len_sq : (double)n_pad * patch) * c;
-  return window_attn_fwd_impl(qkv, win_order, win_inverse, cu_seqlens, nwin, out, n, n_pad, c, heads, patch, scale,
-                              nullptr, dtype, flops, (hipStream_t)stream, lse);
+  WindowAttnCall a = window_attn_call(qkv, win_order, win_inverse, out, n, n_pad, c, heads, patch, scale, dtype, stream);
+  a.cu_seqlens = cu_seqlens; a.num_windows = num_windows; a.sum_len_sq = sum_len_sq; a.lse = lse;
+  return window_attn_forward(a, {"window_attn_train", WA_RAGGED_OPTIONAL, /*lse*/ true});
+}
+
+extern "C" int ptv3_window_attn_drop_fwd(const void* qkv, const int32_t* win_order, const int32_t* win_inverse,
+                                         const int32_t* cu_seqlens, int num_windows, void* out, int64_t n, int64_t n_pad,
+                                         int c, int heads, int patch, float scale, float p_drop, uint32_t seed, int dtype,
+                                         void* stream) {
+  WindowAttnCall a = window_attn_call(qkv, win_order, win_inverse, out, n, n_pad, c, heads, patch, scale, dtype, stream);
+  a.cu_seqlens = cu_seqlens; a.num_windows = num_windows; a.p_drop = p_drop; a.seed = seed;
+  return window_attn_forward(a, {"window_attn_drop", WA_RAGGED_OPTIONAL, false, false, /*drop*/ true});
 }
 
 extern "C" int ptv3_window_attn_rpe_fwd(const void* qkv, const int32_t* win_order, const int32_t* win_inverse,
                                         void* out, int64_t n, int64_t n_pad, int c, int heads, int patch, float scale,
                                         const int32_t* grid_coord, const float* rpe_table, int pos_bnd, int dtype,
                                         void* stream) {
-  PTV3_REQUIRE(heads > 0 && c % heads == 0, "window_attn_rpe: c=%d not divisible by heads=%d", c, heads);
-  PTV3_REQUIRE(patch >= 1 && patch <= 16384, "window_attn_rpe: patch %d outside [1,16384]", patch);
-  PTV3_REQUIRE(n_pad % patch == 0, "window_attn_rpe: n_pad=%lld is not a multiple of patch=%d", (long long)n_pad, patch);
-  PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "window_attn_rpe: bad dtype %d", dtype);
-  PTV3_REQUIRE(grid_coord && rpe_table && pos_bnd >= 0 && pos_bnd <= 4096, "window_attn_rpe: grid_coord, rpe_table and 0 <= pos_bnd <= 4096 are required");
-  const int d = c / heads;
-  if (n == 0) return PTV3_OK;
-  if (d != 16 && d != 32 && d != 64) {
-    set_error("window_attn_rpe: head_dim %d unsupported (16, 32, 64)", d);
-    return PTV3_ERR_UNSUPPORTED;
-  }
-  const int nwin = (int)(n_pad / patch);
-  hipStream_t s = (hipStream_t)stream;
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
-  const int prof = prof_begin(s, PROF_WINDOW_ATTN, 4.0 * n_pad * patch * c,
-                              (double)n_pad * 3 * c * esz + (double)n * c * esz + 4.0 * (n_pad + n) + 12.0 * n_pad,
-                              nullptr, 0, 0.0);
-  const RpeTable rt{grid_coord, rpe_table, pos_bnd};
-  int rc = PTV3_ERR_UNSUPPORTED;
-#define WAR_CASE(T)                                                                                                    \
-  switch (d) {                                                                                                         \
-    case 16: rc = launch_window_attn<T, 1>(qkv, win_order, win_inverse, out, c, heads, patch, nwin, scale, nullptr, s, rt); break; \
-    case 32: rc = launch_window_attn<T, 2>(qkv, win_order, win_inverse, out, c, heads, patch, nwin, scale, nullptr, s, rt); break; \
-    case 64: rc = launch_window_attn<T, 4>(qkv, win_order, win_inverse, out, c, heads, patch, nwin, scale, nullptr, s, rt); break; \
-    default: break;                                                                                                    \
-  }
-  if (dtype == PTV3_F32) { WAR_CASE(float) } else { WAR_CASE(__bf16) }
-#undef WAR_CASE
-  prof_kernel(prof, PK_ATTN_FULL);
-  prof_end(prof, s);
-  return rc;
+  WindowAttnCall a = window_attn_call(qkv, win_order, win_inverse, out, n, n_pad, c, heads, patch, scale, dtype, stream);
+  a.grid_coord = grid_coord; a.rpe_table = rpe_table; a.pos_bnd = pos_bnd;
+  return window_attn_forward(a, {"window_attn_rpe", WA_RAGGED_NO, false, /*rpe*/ true});
 }
+

@@ -137,18 +137,40 @@ def window_plan(order, inverse, offset, offset_host, patch, with_cu=False):
     return (wo, wi, cu) if with_cu else (wo, wi)
 
 
-def window_attention(qkv, win_order, win_inverse, heads, patch, scale, rpe_bias=None):
-    """softmax(scale q k^T) v per window with gather/scatter fused (v3m1_base.py:188-216)."""
+def _attn_check(who, qkv, win_order, win_inverse, heads, patch, cu_seqlens=None, out=None, dout=None, lse=None,
+                grid_coord=None, rpe_table=None, pos_bnd=0):
+    """What every window-attention wrapper checks before a pointer reaches a kernel; a tensor the wrapper does not take
+    stays None.  -> (n, c, n_pad, windows).  A new argument of the operation is checked here (csrc/window_attn.h)."""
     _chk(qkv, "qkv", (torch.float32, torch.bfloat16), 2)
     _chk(win_order, "win_order", torch.int32, 1)
     _chk(win_inverse, "win_inverse", torch.int32, 1)
-    _chk(rpe_bias, "rpe_bias", torch.float32)
+    _chk(cu_seqlens, "cu_seqlens", torch.int32, 1)
+    _chk(out, "out", qkv.dtype, 2)
+    _chk(dout, "dout", qkv.dtype, 2)
+    _chk(lse, "lse", torch.float32, 2)
+    _chk(grid_coord, "grid_coord", torch.int32, 2)
+    _chk(rpe_table, "rpe_table", torch.float32, 2)
     n, c3 = qkv.shape
-    c = c3 // 3
-    if win_inverse.shape[0] != n or c * 3 != c3:
-        raise RuntimeError("window_attention: shape mismatch")
-    n_pad = win_order.shape[0]
-    if rpe_bias is not None and rpe_bias.numel() != (n_pad // patch) * heads * patch * patch:
+    c, n_pad = c3 // 3, win_order.shape[0]
+    bad = c * 3 != c3 or win_inverse.shape[0] != n
+    bad |= cu_seqlens is not None and cu_seqlens.numel() < 2
+    bad |= any(t is not None and tuple(t.shape) != (n, c) for t in (out, dout))
+    bad |= grid_coord is not None and tuple(grid_coord.shape) != (n, 3)
+    bad |= rpe_table is not None and tuple(rpe_table.shape) != (3 * (2 * pos_bnd + 1), heads)
+    if bad:
+        raise RuntimeError(f"{who}: shape mismatch")
+    if lse is not None and tuple(lse.shape) != (n_pad, int(heads)):
+        raise RuntimeError(f"{who}: lse must be (n_pad, heads)")
+    # a patch the library will refuse (outside [1, 16384], or not dividing n_pad) is left to its message
+    nwin = cu_seqlens.numel() - 1 if cu_seqlens is not None else n_pad // max(int(patch), 1)
+    return n, c, n_pad, nwin
+
+
+def window_attention(qkv, win_order, win_inverse, heads, patch, scale, rpe_bias=None):
+    """softmax(scale q k^T) v per window with gather/scatter fused (v3m1_base.py:188-216)."""
+    n, c, n_pad, nwin = _attn_check("window_attention", qkv, win_order, win_inverse, heads, patch)
+    _chk(rpe_bias, "rpe_bias", torch.float32)
+    if rpe_bias is not None and rpe_bias.numel() != nwin * heads * patch * patch:
         raise RuntimeError("window_attention: rpe_bias must be (n_pad/patch, heads, patch, patch)")
     out = torch.empty((n, c), dtype=qkv.dtype, device=qkv.device)
     lib.check(lib.ptv3_window_attn_fwd(_p(qkv), _p(win_order), _p(win_inverse), _p(out), n, n_pad, c, int(heads),
@@ -160,19 +182,11 @@ def window_attention(qkv, win_order, win_inverse, heads, patch, scale, rpe_bias=
 def window_attention_varlen(qkv, win_order, win_inverse, cu_seqlens, heads, max_seqlen, scale, sum_len_sq=0.0):
     """The enable_flash=True call site (v3m1_base.py:207-215): flash_attn_varlen_qkvpacked_func semantics over ragged
     windows [cu_seqlens[w], cu_seqlens[w+1]) of at most max_seqlen padded slots, gather / scatter fused."""
-    _chk(qkv, "qkv", (torch.float32, torch.bfloat16), 2)
-    _chk(win_order, "win_order", torch.int32, 1)
-    _chk(win_inverse, "win_inverse", torch.int32, 1)
-    _chk(cu_seqlens, "cu_seqlens", torch.int32, 1)
-    n, c3 = qkv.shape
-    c = c3 // 3
-    if win_inverse.shape[0] != n or c * 3 != c3 or cu_seqlens.numel() < 2:
-        raise RuntimeError("window_attention_varlen: shape mismatch")
+    n, c, n_pad, nwin = _attn_check("window_attention_varlen", qkv, win_order, win_inverse, heads, max_seqlen, cu_seqlens)
     out = torch.empty((n, c), dtype=qkv.dtype, device=qkv.device)
-    lib.check(lib.ptv3_window_attn_varlen_fwd(_p(qkv), _p(win_order), _p(win_inverse), _p(cu_seqlens),
-                                              cu_seqlens.numel() - 1, _p(out), n, win_order.shape[0], c, int(heads),
-                                              int(max_seqlen), float(scale), float(sum_len_sq), _dt(qkv), _stream()),
-              "ptv3_window_attn_varlen_fwd")
+    lib.check(lib.ptv3_window_attn_varlen_fwd(_p(qkv), _p(win_order), _p(win_inverse), _p(cu_seqlens), nwin, _p(out), n,
+                                              n_pad, c, int(heads), int(max_seqlen), float(scale), float(sum_len_sq),
+                                              _dt(qkv), _stream()), "ptv3_window_attn_varlen_fwd")
     return out
 
 
@@ -186,38 +200,21 @@ def window_attention_any(qkv, win_order, win_inverse, heads, patch, scale, cu_se
 def window_attention_train(qkv, win_order, win_inverse, heads, patch, scale, cu_seqlens=None, sum_len_sq=0.0):
     """The training forward: window_attention_any() that also returns the log-sum-exp rows (n_pad, heads) fp32 the
     backward would otherwise recompute."""
-    _chk(qkv, "qkv", (torch.float32, torch.bfloat16), 2)
-    _chk(win_order, "win_order", torch.int32, 1)
-    _chk(win_inverse, "win_inverse", torch.int32, 1)
-    _chk(cu_seqlens, "cu_seqlens", torch.int32, 1)
-    n, c3 = qkv.shape
-    c = c3 // 3
-    if win_inverse.shape[0] != n:
-        raise RuntimeError("window_attention_train: shape mismatch")
+    n, c, n_pad, nwin = _attn_check("window_attention_train", qkv, win_order, win_inverse, heads, patch, cu_seqlens)
     out = torch.empty((n, c), dtype=qkv.dtype, device=qkv.device)
-    lse = torch.empty((win_order.shape[0], int(heads)), dtype=torch.float32, device=qkv.device)
-    nwin = cu_seqlens.numel() - 1 if cu_seqlens is not None else 0
+    lse = torch.empty((n_pad, int(heads)), dtype=torch.float32, device=qkv.device)
     lib.check(lib.ptv3_window_attn_train_fwd(_p(qkv), _p(win_order), _p(win_inverse), _p(cu_seqlens), nwin, _p(out),
-                                             _p(lse), n, win_order.shape[0], c, int(heads), int(patch), float(scale),
+                                             _p(lse), n, n_pad, c, int(heads), int(patch), float(scale),
                                              float(sum_len_sq), _dt(qkv), _stream()), "ptv3_window_attn_train_fwd")
     return out, lse
 
 
 def window_attention_train_bwd(qkv, out, dout, lse, win_order, win_inverse, heads, patch, scale, cu_seqlens=None):
-    _chk(qkv, "qkv", (torch.float32, torch.bfloat16), 2)
-    _chk(out, "out", qkv.dtype, 2)
-    _chk(dout, "dout", qkv.dtype, 2)
-    _chk(lse, "lse", torch.float32, 2)
-    _chk(cu_seqlens, "cu_seqlens", torch.int32, 1)
-    n, c3 = qkv.shape
-    c = c3 // 3
-    n_pad = win_order.shape[0]
-    if tuple(lse.shape) != (n_pad, int(heads)):
-        raise RuntimeError("window_attention_train_bwd: lse must be (n_pad, heads)")
+    n, c, n_pad, nwin = _attn_check("window_attention_train_bwd", qkv, win_order, win_inverse, heads, patch, cu_seqlens,
+                                    out, dout, lse)
     dqkv = torch.empty_like(qkv)
     nb = lib.ptv3_window_attn_bwd_workspace_bytes(n, n_pad, c, int(heads), _dt(qkv))
     ws = _ws(nb, qkv.device)
-    nwin = cu_seqlens.numel() - 1 if cu_seqlens is not None else 0
     lib.check(lib.ptv3_window_attn_train_bwd(_p(qkv), _p(out), _p(dout), _p(lse), _p(win_order), _p(win_inverse),
                                              _p(cu_seqlens), nwin, _p(dqkv), n, n_pad, c, int(heads), int(patch),
                                              float(scale), _dt(qkv), _p(ws), nb, _stream()), "ptv3_window_attn_train_bwd")
@@ -227,34 +224,20 @@ def window_attention_train_bwd(qkv, out, dout, lse, win_order, win_inverse, head
 def window_attention_drop(qkv, win_order, win_inverse, heads, patch, scale, p_drop, seed, cu_seqlens=None):
     """Training forward with attention dropout (:203 / :211): softmax over all pairs, kept pairs / (1 - p_drop) into the
     value sum; the keep mask is a hash of (query slot, head, key slot, seed) - see drop_keep_mask()."""
-    _chk(qkv, "qkv", (torch.float32, torch.bfloat16), 2)
-    _chk(win_order, "win_order", torch.int32, 1)
-    _chk(win_inverse, "win_inverse", torch.int32, 1)
-    _chk(cu_seqlens, "cu_seqlens", torch.int32, 1)
-    n, c3 = qkv.shape
-    c = c3 // 3
-    if win_inverse.shape[0] != n:
-        raise RuntimeError("window_attention_drop: shape mismatch")
+    n, c, n_pad, nwin = _attn_check("window_attention_drop", qkv, win_order, win_inverse, heads, patch, cu_seqlens)
     out = torch.empty((n, c), dtype=qkv.dtype, device=qkv.device)
-    nwin = cu_seqlens.numel() - 1 if cu_seqlens is not None else 0
     lib.check(lib.ptv3_window_attn_drop_fwd(_p(qkv), _p(win_order), _p(win_inverse), _p(cu_seqlens), nwin, _p(out), n,
-                                            win_order.shape[0], c, int(heads), int(patch), float(scale), float(p_drop),
+                                            n_pad, c, int(heads), int(patch), float(scale), float(p_drop),
                                             int(seed) & 0xFFFFFFFF, _dt(qkv), _stream()), "ptv3_window_attn_drop_fwd")
     return out
 
 
 def window_attention_drop_bwd(qkv, out, dout, win_order, win_inverse, heads, patch, scale, p_drop, seed, cu_seqlens=None):
-    _chk(qkv, "qkv", (torch.float32, torch.bfloat16), 2)
-    _chk(out, "out", qkv.dtype, 2)
-    _chk(dout, "dout", qkv.dtype, 2)
-    _chk(cu_seqlens, "cu_seqlens", torch.int32, 1)
-    n, c3 = qkv.shape
-    c = c3 // 3
-    n_pad = win_order.shape[0]
+    n, c, n_pad, nwin = _attn_check("window_attention_drop_bwd", qkv, win_order, win_inverse, heads, patch, cu_seqlens,
+                                    out, dout)
     dqkv = torch.empty_like(qkv)
     nb = lib.ptv3_window_attn_bwd_workspace_bytes(n, n_pad, c, int(heads), _dt(qkv))
     ws = _ws(nb, qkv.device)
-    nwin = cu_seqlens.numel() - 1 if cu_seqlens is not None else 0
     lib.check(lib.ptv3_window_attn_drop_bwd(_p(qkv), _p(out), _p(dout), _p(win_order), _p(win_inverse), _p(cu_seqlens),
                                             nwin, _p(dqkv), n, n_pad, c, int(heads), int(patch), float(scale),
                                             float(p_drop), int(seed) & 0xFFFFFFFF, _dt(qkv), _p(ws), nb, _stream()),
@@ -283,20 +266,12 @@ def drop_keep_mask(slot, head, key, heads, seed, p_drop):
 def window_attention_rpe(qkv, win_order, win_inverse, heads, patch, scale, grid_coord, rpe_table, pos_bnd):
     """window_attention() + the RPE bias looked up from the (3*(2*pos_bnd+1), heads) table inside the kernel.
     Returns None when the window does not fit the resident-window kernel (caller falls back to the dense bias)."""
-    _chk(qkv, "qkv", (torch.float32, torch.bfloat16), 2)
-    _chk(win_order, "win_order", torch.int32, 1)
-    _chk(win_inverse, "win_inverse", torch.int32, 1)
-    _chk(grid_coord, "grid_coord", torch.int32, 2)
-    _chk(rpe_table, "rpe_table", torch.float32, 2)
-    n, c3 = qkv.shape
-    c = c3 // 3
-    if win_inverse.shape[0] != n or tuple(grid_coord.shape) != (n, 3) or \
-            tuple(rpe_table.shape) != (3 * (2 * pos_bnd + 1), heads):
-        raise RuntimeError("window_attention_rpe: shape mismatch")
+    n, c, n_pad, _ = _attn_check("window_attention_rpe", qkv, win_order, win_inverse, heads, patch,
+                                 grid_coord=grid_coord, rpe_table=rpe_table, pos_bnd=pos_bnd)
     out = torch.empty((n, c), dtype=qkv.dtype, device=qkv.device)
-    rc = lib.ptv3_window_attn_rpe_fwd(_p(qkv), _p(win_order), _p(win_inverse), _p(out), n, win_order.shape[0], c,
-                                      int(heads), int(patch), float(scale), _p(grid_coord), _p(rpe_table),
-                                      int(pos_bnd), _dt(qkv), _stream())
+    rc = lib.ptv3_window_attn_rpe_fwd(_p(qkv), _p(win_order), _p(win_inverse), _p(out), n, n_pad, c, int(heads),
+                                      int(patch), float(scale), _p(grid_coord), _p(rpe_table), int(pos_bnd), _dt(qkv),
+                                      _stream())
     if rc == 3:   # PTV3_ERR_UNSUPPORTED
         return None
     lib.check(rc, "ptv3_window_attn_rpe_fwd")
@@ -835,25 +810,15 @@ def segment_sum(dy, order0, seg_start, n_out):
 
 
 def window_attention_bwd(qkv, out, dout, win_order, win_inverse, heads, patch, scale, cu_seqlens=None):
-    _chk(qkv, "qkv", _F, 2)
-    _chk(cu_seqlens, "cu_seqlens", torch.int32, 1)
-    _chk(out, "out", qkv.dtype, 2)
-    _chk(dout, "dout", qkv.dtype, 2)
-    _chk(win_order, "win_order", torch.int32, 1)
-    _chk(win_inverse, "win_inverse", torch.int32, 1)
-    n, c3 = qkv.shape
-    c = c3 // 3
-    n_pad = win_order.shape[0]
-    if out.shape != (n, c) or dout.shape != (n, c) or win_inverse.shape[0] != n:
-        raise RuntimeError("window_attention_bwd: shape mismatch")
+    n, c, n_pad, nwin = _attn_check("window_attention_bwd", qkv, win_order, win_inverse, heads, patch, cu_seqlens, out, dout)
     dqkv = torch.empty_like(qkv)
     nb = lib.ptv3_window_attn_bwd_workspace_bytes(n, n_pad, c, int(heads), _dt(qkv))
     ws = _ws(nb, qkv.device)
     if cu_seqlens is not None:
         lib.check(lib.ptv3_window_attn_varlen_bwd(_p(qkv), _p(out), _p(dout), _p(win_order), _p(win_inverse),
-                                                  _p(cu_seqlens), cu_seqlens.numel() - 1, _p(dqkv), n, n_pad, c,
-                                                  int(heads), int(patch), float(scale), _dt(qkv), _p(ws), nb,
-                                                  _stream()), "ptv3_window_attn_varlen_bwd")
+                                                  _p(cu_seqlens), nwin, _p(dqkv), n, n_pad, c, int(heads), int(patch),
+                                                  float(scale), _dt(qkv), _p(ws), nb, _stream()),
+                  "ptv3_window_attn_varlen_bwd")
         return dqkv
     lib.check(lib.ptv3_window_attn_bwd(_p(qkv), _p(out), _p(dout), _p(win_order), _p(win_inverse), _p(dqkv), n, n_pad,
                                        c, int(heads), int(patch), float(scale), _dt(qkv), _p(ws), nb, _stream()),
@@ -864,19 +829,8 @@ def window_attention_bwd(qkv, out, dout, win_order, win_inverse, heads, patch, s
 def window_attention_rpe_bwd(qkv, out, dout, win_order, win_inverse, heads, patch, scale, grid_coord, rpe_table,
                              pos_bnd):
     """-> (dqkv (n, 3c), dtable (3*(2*pos_bnd+1), heads) fp32) of window_attention_rpe."""
-    _chk(qkv, "qkv", _F, 2)
-    _chk(out, "out", qkv.dtype, 2)
-    _chk(dout, "dout", qkv.dtype, 2)
-    _chk(win_order, "win_order", torch.int32, 1)
-    _chk(win_inverse, "win_inverse", torch.int32, 1)
-    _chk(grid_coord, "grid_coord", torch.int32, 2)
-    _chk(rpe_table, "rpe_table", torch.float32, 2)
-    n, c3 = qkv.shape
-    c = c3 // 3
-    n_pad = win_order.shape[0]
-    if out.shape != (n, c) or dout.shape != (n, c) or win_inverse.shape[0] != n or tuple(grid_coord.shape) != (n, 3) \
-            or tuple(rpe_table.shape) != (3 * (2 * pos_bnd + 1), heads):
-        raise RuntimeError("window_attention_rpe_bwd: shape mismatch")
+    n, c, n_pad, _ = _attn_check("window_attention_rpe_bwd", qkv, win_order, win_inverse, heads, patch, None, out, dout,
+                                 grid_coord=grid_coord, rpe_table=rpe_table, pos_bnd=pos_bnd)
     dqkv = torch.empty_like(qkv)
     dtable = torch.empty_like(rpe_table)
     nb = lib.ptv3_window_attn_rpe_bwd_workspace_bytes(n, n_pad, c, int(heads), int(patch), int(pos_bnd), _dt(qkv))

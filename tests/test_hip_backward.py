@@ -188,6 +188,106 @@ def test_window_attention_backward(dev, sizes, C, H, K):
     _close(qb.grad, qr.grad, tol=5e-2, what="dqkv bf16")
 
 
+@pytest.fixture(scope="module")
+def tiny_attn(dev):
+    """One window of 8 points, 16 channels, one head, fp32, with float64 references of every form of the call
+    (tests/window_attn_ref.py; the dropout mask is ops.drop_keep_mask's, the RPE bias the table lookup written out)."""
+    import window_attn_ref as R
+    from ptv3_hip import ops
+    n = K = 8
+    C, H, bnd, p, seed = 16, 1, 2, 0.5, 7
+    scale = (C // H) ** -0.5
+    plan = R.make_plan([n], K, seed=3)
+    g = torch.Generator().manual_seed(11)
+    qkv, dout = torch.randn(n, 3 * C, generator=g), torch.randn(n, C, generator=g)
+    grid = torch.randint(0, 6, (n, 3), generator=g, dtype=torch.int32)
+    table = torch.randn(3 * (2 * bnd + 1), H, generator=g)
+    o = plan["order"][plan["pad"]]
+    rel = (grid[o].long()[:, None, :] - grid[o].long()[None, :, :]).clamp(-bnd, bnd) + bnd               # (K, K, 3)
+    bias = sum(table[d * (2 * bnd + 1) + rel[..., d], 0] for d in range(3)).double()[None, None]       # (1, H, K, K)
+    keep = ops.drop_keep_mask(np.arange(K)[:, None], 0, np.arange(K)[None, :], H, seed, p)
+    mask = torch.from_numpy(keep.astype(np.float64)) / (1.0 - float(np.float32(p)))
+
+    def ref(kind):
+        q = qkv.double().requires_grad_(True)
+        args = (plan["order"], plan["inverse"], plan["pad"], plan["unpad"], H, K, scale)
+        if kind == "drop":    # softmax over all pairs, kept pairs / (1 - p) into the value sum; no borrowed slot here
+            a, b, v = q[o].reshape(K, 3, C).unbind(1)
+            out = ((torch.softmax(a @ b.T * scale, dim=-1) * mask) @ v)[plan["unpad"][plan["inverse"]]]
+            lse = None
+        else:
+            out, lse = R.attention_f64(q, *args, bias=bias if kind == "rpe" else None)
+        out.backward(dout.double())
+        return out.detach(), None if lse is None else lse.detach(), q.grad
+
+    t = lambda a: a.to(dev)  # noqa: E731
+    wo, wi = ops.window_maps(t(plan["order"]), t(plan["inverse"]), t(plan["pad"]), t(plan["unpad"]))
+    return dict(n=n, K=K, C=C, H=H, bnd=bnd, p=p, seed=seed, scale=scale, qkv=t(qkv), dout=t(dout), grid=t(grid),
+                table=t(table), wo=wo, wi=wi, cu=t(plan["cu"]), ref={k: ref(k) for k in ("plain", "rpe", "drop")})
+
+
+_ATTN_WRAPPERS = ["window_attention", "window_attention_varlen", "window_attention_train", "window_attention_train_bwd",
+                  "window_attention_drop", "window_attention_drop_bwd", "window_attention_rpe", "window_attention_bwd",
+                  "window_attention_rpe_bwd"]
+
+
+@pytest.mark.parametrize("name", _ATTN_WRAPPERS)
+def test_window_attention_wrappers_refuse_wrong_shapes_on_the_host(dev, tiny_attn, name):
+    """Every wrapper of the window attention raises on the host for a win_inverse one element short, an int64 win_order,
+    a qkv of width 47 and, where it takes them, an out / dout of (n-1, c) and an lse of (n_pad, heads+1).  After every
+    refusal a valid call of the same wrapper must still give the reference result: nothing was launched on the bad
+    tensors (an out-of-bounds write would show there, or fault).
+    Tolerance: a score is a 16-term fp32 dot product of at most ~8 log2 units, off by at most 16 * 2^-24 * 8 = 7.6e-6;
+    exp2 carries that times ln 2 = 5.3e-6 relative into P, the 8- and 16-term sums add 24 * 2^-24 = 1.4e-6: below 1e-5
+    of the result's scale for the forward, twice that for the gradient, which goes through two such products."""
+    from ptv3_hip import ops
+    d = tiny_attn
+    fn = getattr(ops, name)
+    kind = "rpe" if "rpe" in name else ("drop" if "drop" in name else "plain")
+    out_ref, lse_ref, dq_ref = d["ref"][kind]
+    good = dict(qkv=d["qkv"], win_order=d["wo"], win_inverse=d["wi"])
+    if name.endswith("_bwd"):
+        good.update(out=out_ref.float().to(dev), dout=d["dout"])
+    if name == "window_attention_train_bwd":
+        good.update(lse=lse_ref.float().to(dev))
+    bad = [("win_inverse", d["wi"][:-1].contiguous()), ("win_order", d["wo"].long()),
+           ("qkv", torch.randn(d["n"], 47, device=dev))]
+    for k in ("out", "dout"):
+        if k in good:
+            bad.append((k, good[k][:-1].contiguous()))
+    if "lse" in good:
+        bad.append(("lse", torch.zeros(d["K"], d["H"] + 1, device=dev)))
+
+    def call(t):
+        tail = dict(window_attention=(), window_attention_bwd=(),
+                    window_attention_train=(), window_attention_train_bwd=(),
+                    window_attention_drop=(d["p"], d["seed"]), window_attention_drop_bwd=(d["p"], d["seed"]),
+                    window_attention_rpe=(d["grid"], d["table"], d["bnd"]),
+                    window_attention_rpe_bwd=(d["grid"], d["table"], d["bnd"]))
+        if name == "window_attention_varlen":
+            return fn(t["qkv"], t["win_order"], t["win_inverse"], d["cu"], d["H"], d["K"], d["scale"])
+        lead = [t["qkv"]] + [t[k] for k in ("out", "dout") if k in t]
+        if name == "window_attention_train_bwd":
+            lead.append(t["lse"])
+        return fn(*lead, t["win_order"], t["win_inverse"], d["H"], d["K"], d["scale"], *tail[name])
+
+    def check_valid():
+        got = call(good)
+        torch.cuda.synchronize()
+        if name.endswith("_bwd"):
+            _close(got[0] if isinstance(got, tuple) else got, dq_ref.float(), tol=2e-5, what=f"{name} dqkv")
+        else:
+            _close(got[0] if isinstance(got, tuple) else got, out_ref.float(), tol=1e-5, what=f"{name} out")
+        if name == "window_attention_train":
+            _close(got[1], lse_ref.float(), tol=1e-5, what="lse")
+
+    check_valid()
+    for key, tensor in bad:
+        with pytest.raises((RuntimeError, TypeError)):
+            call(dict(good, **{key: tensor}))
+        check_valid()
+
+
 @pytest.mark.parametrize("sizes,C,H,K", [([300, 200], 32, 2, 64), ([2100], 64, 4, 1024), ([130, 77, 300], 64, 2, 50)])
 def test_window_attention_train_forward_leaves_the_log_sum_exp(dev, sizes, C, H, K):
     """ptv3_window_attn_train_fwd: the same output as the eval entry point plus, per (padded slot, head), the log2-domain
