@@ -57,6 +57,20 @@ size_t ptv3_argsort_workspace_bytes(int k, int64_t n);
 int ptv3_argsort_i64(const int64_t* code, int k, int64_t n, int end_bit, int64_t* order,
                      int64_t* inverse, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The executor's form of ptv3_argsort_i64, order and inverse bit for bit the same.
+ * row_order (optional, NULL = skip): (n) int32, row 0 of `order` once more: the gather order of the sparse
+ * convolutions, written by the last pass.  ptv3_argsort_scan_batch: per-block counters a scatter workgroup loads per
+ * round trip when it derives its own digit bases (the sizes on both sides of a multiple of it x 2048 keys take
+ * different trips). */
+int ptv3_argsort_i64_rows(const int64_t* code, int k, int64_t n, int end_bit, int64_t* order, int64_t* inverse,
+                          int32_t* row_order, void* workspace, size_t workspace_bytes, void* stream);
+int ptv3_argsort_scan_batch(void);
+
+/* max(0, largest of the 3n grid coordinates) -> out_max[0] (int32, device or pinned host memory):
+ * serialization depth = bit_length(max + 1) (models/utils/structure.py:73).  int64 coordinates are read as int32.
+ * state: two device int32 that are zero before the call; the call leaves them zero again (one launch, no fill). */
+int ptv3_coord_max(const void* grid_coord, int coord_is_i64, int64_t n, int32_t* state, int32_t* out_max, void* stream);
+
 /* ---- patch partition ----------------------------------------------------------------------
  * replaces SerializedAttention.get_padding_and_inverse (point_transformer_v3m1_base.py:114-170).
  * offset: (b) int64 cumulative scene ends (device); patch = K.  A scene of n_b > K points is padded to a
@@ -142,6 +156,15 @@ size_t ptv3_subm_block_table_bytes(int64_t n);
 int ptv3_subm_build_block_table(const int32_t* indices, int64_t n, void* table, size_t bytes, void* stream);
 int ptv3_subm_neighbors_blocks(const int32_t* indices, int64_t n, const void* table, size_t bytes, int ksize,
                                int32_t* nbr, void* stream);
+
+/* The executor's form of the table build: ptv3_subm_sites writes indices[i] = (batch[i], grid_coord[i]) as int32
+ * (16-byte aligned), optionally the coordinates as (n,3) int64 (grid64, NULL = skip), and zero-fills `table` in the same
+ * launch; ptv3_subm_build_block_table_zeroed then builds the table without a fill of its own.  The table is bit for bit
+ * the one ptv3_subm_build_block_table builds up to the order of its payload ranges, and the neighbour tables read from
+ * it are bit for bit the same. */
+int ptv3_subm_sites(const int64_t* batch, const void* grid_coord, int coord_is_i64, int64_t n, int32_t* indices,
+                    int64_t* grid64, void* table, size_t bytes, void* stream);
+int ptv3_subm_build_block_table_zeroed(const int32_t* indices, int64_t n, void* table, size_t bytes, void* stream);
 
 /* y = epilogue( sum_{d<kvol} sum_{c<cin} w[o][d][c] * x[nbr[i][d]][c] ).
  *   nbr == NULL, kvol == 1  ->  plain torch.nn.Linear: y = x @ w^T            (w: (cout, cin))

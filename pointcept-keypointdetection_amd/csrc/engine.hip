@@ -59,16 +59,54 @@ __global__ void i64_to_i32_kernel(const int64_t* __restrict__ src, int32_t* __re
   if (i < n) dst[i] = (int32_t)src[i];
 }
 
-// max over all 3n grid coordinates -> out[0] (for depth = bit_length(max + 1), structure.py:73)
-__global__ void coord_max_kernel(const void* __restrict__ grid, int is_i64, int64_t n3, int* __restrict__ out) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// max(0, largest of the 3n grid coordinates) -> out[0] (for depth = bit_length(max + 1), structure.py:73).
+// One pass: CM_BATCH values per thread, all loads in flight at once from a clamped index (a slot past the end reads the
+// last value again, which changes no maximum); reduced in the wave, across the waves in LDS, one atomicMax per workgroup.
+// (A grid-stride loop was five dependent round trips at 100k points, and 1024 atomics on one address.)
+// state = {running maximum, workgroups done}, both zero before the launch.  The workgroup that arrives last holds the
+// result: it writes it to out, copies the b scene offsets to offset_out (out and offset_out may be pinned host memory:
+// the launch then IS the read-back, no zero fill and no copy in front of or behind it) and zeroes state for the next launch.
+constexpr int CM_BATCH = 8;
+template <typename CoordT>
+__global__ void __launch_bounds__(256) coord_max_kernel(const CoordT* __restrict__ grid, int64_t n3, int* __restrict__ state,
+                                                        int* __restrict__ out, const int64_t* __restrict__ offset, int b,
+                                                        int64_t* __restrict__ offset_out) {
+  __shared__ int s_wave[4];
+  __shared__ int s_last;
+  const int64_t base = (int64_t)blockIdx.x * (256 * CM_BATCH) + threadIdx.x;
+  CoordT c[CM_BATCH];
+#pragma unroll
+  for (int u = 0; u < CM_BATCH; ++u) c[u] = grid[min(base + u * 256, n3 - 1)];
   int v = 0;
-  for (; i < n3; i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t c = is_i64 ? ((const int64_t*)grid)[i] : (int64_t)((const int32_t*)grid)[i];
-    v = max(v, (int)c);
-  }
+#pragma unroll
+  for (int u = 0; u < CM_BATCH; ++u) v = max(v, (int)c[u]);
   for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_down(v, d, 64));
-  if ((threadIdx.x & 63) == 0) atomicMax(out, v);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    atomicMax(&state[0], max(max(s_wave[0], s_wave[1]), max(s_wave[2], s_wave[3])));
+    __threadfence();   // this workgroup's maximum is in place before its arrival counts
+    const bool last = atomicAdd(&state[1], 1) == (int)gridDim.x - 1;
+    if (last) {
+      __threadfence();
+      out[0] = atomicExch(&state[0], 0);   // every workgroup's atomicMax precedes its arrival: the exchange sees them all
+      atomicExch(&state[1], 0);
+    }
+    s_last = last;
+  }
+  __syncthreads();
+  if (s_last)
+    for (int i = threadIdx.x; i < b; i += 256) offset_out[i] = offset[i];
+}
+static void coord_max(const void* grid, int is_i64, int64_t n, int* state, int* out, const int64_t* offset, int b,
+                      int64_t* offset_out, hipStream_t s) {
+  const dim3 blocks((unsigned)cdiv(3 * n, 256 * CM_BATCH));
+  if (is_i64)
+    hipLaunchKernelGGL(coord_max_kernel<int64_t>, blocks, dim3(256), 0, s, (const int64_t*)grid, 3 * n, state, out, offset,
+                       b, offset_out);
+  else
+    hipLaunchKernelGGL(coord_max_kernel<int32_t>, blocks, dim3(256), 0, s, (const int32_t*)grid, 3 * n, state, out, offset,
+                       b, offset_out);
 }
 
 // batch[i] = scene of point i, from the cumulative offsets (offset2batch, models/utils/misc.py:25-30)
@@ -149,6 +187,34 @@ struct Exec {
   bool last_overlap = false;  // mode of the previous call (the overlap handshake reruns after a stream-ordered call)
   double sync_us = 0.0;       // host time blocked in geometry-stream read-backs (PTV3_ENGINE_TIMING=1)
   std::mutex mu;
+  // pinned landing place of the level-0 read-backs (coordinate maximum, scene offsets): a pageable destination is
+  // staged by the runtime.  Read by the host inside the call that filled it, under `mu`.
+  void* pinned = nullptr; size_t pinned_cap = 0;
+  // {maximum, arrivals} of coord_max_kernel: zero between launches (the kernel resets it), so no fill precedes a launch
+  int* cm_state = nullptr;
+  int* coord_max_state() {
+    if (!cm_state) {
+      if (hipMalloc((void**)&cm_state, 256) != hipSuccess) { cm_state = nullptr; return nullptr; }
+      if (hipMemset(cm_state, 0, 256) != hipSuccess) { (void)hipFree(cm_state); cm_state = nullptr; }
+    }
+    return cm_state;
+  }
+  void* pinned_at_least(size_t bytes) {
+    if (pinned_cap < bytes) {
+      if (pinned) (void)hipHostFree(pinned);
+      pinned = nullptr; pinned_cap = 0;
+      const size_t cap = std::max<size_t>(bytes, 4096);
+      if (hipHostMalloc(&pinned, cap, hipHostMallocDefault) != hipSuccess) { pinned = nullptr; return nullptr; }
+      pinned_cap = cap;
+    }
+    return pinned;
+  }
+  hipError_t timed_event_sync(hipEvent_t e) {
+    double t = now_us();
+    hipError_t r = hipEventSynchronize(e);
+    sync_us += now_us() - t;
+    return r;
+  }
   hipError_t timed_sync(hipStream_t s) {
     double t = now_us();
     hipError_t e = hipStreamSynchronize(s);
@@ -169,6 +235,8 @@ struct Exec {
     for (auto& f : feat) if (f) { (void)hipStreamSynchronize(f); f = nullptr; }
     for (hipEvent_t e : events) (void)hipEventDestroy(e);
     events.clear();
+    if (pinned) { (void)hipHostFree(pinned); pinned = nullptr; pinned_cap = 0; }
+    if (cm_state) { (void)hipFree(cm_state); cm_state = nullptr; }
   }
 };
 static std::mutex g_exec_mutex;
@@ -265,27 +333,25 @@ struct Run {
     for (int i = 0; i < k; ++i) { P.wo[i] = wo + (int64_t)i * n_pad; P.wi[i] = wi + (int64_t)i * L.n; }
   }
 
-  // sites, hash, neighbour tables and window plans of one level (geometry stream)
   hipEvent_t stem_ready = nullptr;
-  void level_geometry(Level& L, int st, const void* grid_in, int is_i64, bool need_grid64) {
+  // Level 0, the part that needs coordinates and batch ids only: sites, block table, 5^3 table.  It is queued before
+  // the host has read the depth and the offsets back, so it runs while the host waits.  One launch converts the sites
+  // and zero-fills the table (ptv3_subm_sites); row_order is written later, by the last pass of the sort.
+  void level0_sites(Level& L, const void* grid_in, int is_i64) {
     L.indices = (int32_t*)G->alloc((size_t)L.n * 16);
     L.row_order = (int32_t*)G->alloc((size_t)L.n * 4);
-    int64_t* g64 = nullptr;
-    if (need_grid64) { g64 = (int64_t*)G->alloc((size_t)L.n * 24); L.grid = g64; }
-    if (!dry && ok())
-      hipLaunchKernelGGL(make_indices_kernel, dim3((unsigned)cdiv(L.n, 256)), dim3(256), 0, sg, L.batch, grid_in, is_i64,
-                         L.n, L.indices, g64, L.row_order, L.order);
-    // neighbour tables through the block table at every level: its kernels write whole rows (no -1 pre-fill) and touch
-    // a fifth of the lines of the per-voxel probes, which headed the forward's critical path at the 5^3 stem
+    int64_t* g64 = (int64_t*)G->alloc((size_t)L.n * 24);
+    L.grid = g64;
     L.table_bytes = ptv3_subm_block_table_bytes(L.n);
     L.table = G->alloc(L.table_bytes);
-    RUN(ptv3_subm_build_block_table(L.indices, L.n, L.table, L.table_bytes, sg));
-    if (st == 0) {
-      L.nbr5 = (int32_t*)G->alloc((size_t)L.n * 125 * 4);
-      RUN(ptv3_subm_neighbors_blocks(L.indices, L.n, L.table, L.table_bytes, 5, L.nbr5, sg));
-      // the stem conv needs the 5^3 table and the row order only: it starts here, under the 3^3 table and the window plans
-      if (!dry && ok() && stem_ready) (void)hipEventRecord(stem_ready, sg);
-    }
+    RUN(ptv3_subm_sites(L.batch, grid_in, is_i64, L.n, L.indices, g64, L.table, L.table_bytes, sg));
+    RUN(ptv3_subm_build_block_table_zeroed(L.indices, L.n, L.table, L.table_bytes, sg));
+    L.nbr5 = (int32_t*)G->alloc((size_t)L.n * 125 * 4);
+    RUN(ptv3_subm_neighbors_blocks(L.indices, L.n, L.table, L.table_bytes, 5, L.nbr5, sg));
+  }
+
+  // 3^3 table and window plans of one level whose sites and block table exist
+  void level_tables(Level& L, int st) {
     L.nbr3 = (int32_t*)G->alloc((size_t)L.n * 27 * 4);
     RUN(ptv3_subm_neighbors_blocks(L.indices, L.n, L.table, L.table_bytes, 3, L.nbr3, sg));
     const int Ke = patch_K(L, d->enc_patch[st]);
@@ -294,6 +360,21 @@ struct Run {
       const int Kd = patch_K(L, d->dec_patch[st]);
       if (Kd == Ke) L.plan[1] = L.plan[0]; else window_plan(L, L.plan[1], Kd);
     }
+  }
+
+  // sites, block table, neighbour table and window plans of a pooled level (geometry stream)
+  void level_geometry(Level& L, int st, const void* grid_in, int is_i64) {
+    L.indices = (int32_t*)G->alloc((size_t)L.n * 16);
+    L.row_order = (int32_t*)G->alloc((size_t)L.n * 4);
+    if (!dry && ok())
+      hipLaunchKernelGGL(make_indices_kernel, dim3((unsigned)cdiv(L.n, 256)), dim3(256), 0, sg, L.batch, grid_in, is_i64,
+                         L.n, L.indices, (int64_t*)nullptr, L.row_order, L.order);
+    // neighbour tables through the block table at every level: its kernels write whole rows (no -1 pre-fill) and touch
+    // a fifth of the lines of the per-voxel probes, which headed the forward's critical path at the 5^3 stem
+    L.table_bytes = ptv3_subm_block_table_bytes(L.n);
+    L.table = G->alloc(L.table_bytes);
+    RUN(ptv3_subm_build_block_table(L.indices, L.n, L.table, L.table_bytes, sg));
+    level_tables(L, st);
   }
 
   // SerializedAttention core (:184-216): uniform K-slot windows, or ragged ones (a scene shorter than the fixed patch
@@ -420,32 +501,41 @@ static int run_forward(Exec* X, const ptv3_model_desc* d, const void* const* par
   L0.code = io->code; L0.order = io->order; L0.inverse = io->inverse;
   L0.off_host.resize(io->b);
   int depth = io->depth;
+  // Order on the geometry stream: coordinate maximum, whose last workgroup writes the maximum and the offsets into the
+  // executor's pinned buffer (a copy only where the depth is given and the offsets are not), and an event; then
+  // everything of level 0 that needs neither the depth nor validated offsets (batch ids, sites + table zero fill, block
+  // table, 5^3 table); the host waits for the event alone and validates; then curve codes and the sort, whose last pass
+  // leaves row_order: the stem conv may start; then the 3^3 table and the window plans.
+  // The kernels queued ahead of the validation run for ANY int32 coordinates and any offsets, and a failed validation
+  // returns with them in flight; they stay inside this call's arena: batch_from_offset_kernel and bt_sites_kernel index by
+  // the point (< n) and read offset[0 .. b) only; the block-table kernels reach the slots through `& smask`, a bit
+  // through `& 3` fields, the payload through base + rank < (bits set) <= n (sparse.hip), and bt_neighbors_kernel
+  // range-checks every tap before it looks anything up and writes n x 125 entries by position.
+  const int* hmax = nullptr; const int64_t* hoff = nullptr;
+  hipEvent_t read_back = nullptr;
   if (dry) {
     for (int i = 0; i < io->b; ++i) L0.off_host[i] = io->offset_host ? io->offset_host[i] : io->n * (i + 1) / io->b;
-    if (depth <= 0) { depth = 16; G.alloc(256); }
+    if (depth <= 0) depth = 16;
   } else {
-    int* dmax = nullptr;
-    if (depth <= 0) {
-      dmax = (int*)G.alloc(256);
-      if (G.failed) { set_error("forward: workspace arena too small"); return PTV3_ERR_ARG; }
-      (void)hipMemsetAsync(dmax, 0, 4, sg);
-      hipLaunchKernelGGL(coord_max_kernel, dim3(256), dim3(256), 0, sg, io->grid_coord, io->coord_is_i64, 3 * io->n, dmax);
-    }
-    int hmax = 0;
-    if (dmax) (void)hipMemcpyAsync(&hmax, dmax, 4, hipMemcpyDeviceToHost, sg);
     if (io->offset_host) std::copy(io->offset_host, io->offset_host + io->b, L0.off_host.begin());
-    else (void)hipMemcpyAsync(L0.off_host.data(), io->offset, (size_t)io->b * 8, hipMemcpyDeviceToHost, sg);
-    if (dmax || !io->offset_host) {
-      if (X->timed_sync(sg) != hipSuccess) { set_error("forward: input read-back failed"); return PTV3_ERR_LAUNCH; }
+    if (depth <= 0 || !io->offset_host) {
+      char* pin = (char*)X->pinned_at_least(8 + (size_t)io->b * 8);
+      if (!pin) { set_error("forward: cannot allocate the pinned read-back buffer"); return PTV3_ERR_LAUNCH; }
+      if (!io->offset_host) hoff = (const int64_t*)(pin + 8);
+      if (depth <= 0) {
+        // the kernel's last workgroup writes the maximum and the offsets into the pinned buffer itself
+        int* state = X->coord_max_state();
+        if (!state) { set_error("forward: cannot allocate the coordinate-maximum state"); return PTV3_ERR_LAUNCH; }
+        hmax = (const int*)pin;
+        coord_max(io->grid_coord, io->coord_is_i64, io->n, state, (int*)pin, io->offset, hoff ? io->b : 0,
+                  (int64_t*)(pin + 8), sg);
+      } else {
+        (void)hipMemcpyAsync(pin + 8, io->offset, (size_t)io->b * 8, hipMemcpyDeviceToHost, sg);
+      }
+      read_back = X->event_at(18);
+      (void)hipEventRecord(read_back, sg);
     }
-    if (dmax) { depth = 0; for (unsigned v = (unsigned)hmax + 1; v; v >>= 1) ++depth; }
-    PTV3_REQUIRE(depth >= 1 && depth <= 16, "forward: serialization depth %d outside [1,16] (structure.py:81)", depth);
-    for (int i = 0; i < io->b; ++i)
-      PTV3_REQUIRE(L0.off_host[i] > (i ? L0.off_host[i - 1] : 0), "forward: empty scene %d", i);
-    PTV3_REQUIRE(L0.off_host[io->b - 1] == io->n, "forward: offset does not end at n");
   }
-  L0.depth = depth;
-  if (io->depth_out) *io->depth_out = depth;
   if (io->batch == nullptr) {  // derive the batch ids on the geometry stream (no torch ops on the caller's stream)
     int64_t* bt = io->batch_out ? io->batch_out : (int64_t*)G.alloc((size_t)io->n * 8);
     if (!dry && R.ok())
@@ -453,14 +543,32 @@ static int run_forward(Exec* X, const ptv3_model_desc* d, const void* const* par
                          io->n, bt);
     L0.batch = bt;
   }
+  R.level0_sites(L0, io->grid_coord, io->coord_is_i64);
+  if (!dry) {
+    if (read_back && X->timed_event_sync(read_back) != hipSuccess) {
+      set_error("forward: input read-back failed");
+      return PTV3_ERR_LAUNCH;
+    }
+    if (hoff) std::copy(hoff, hoff + io->b, L0.off_host.begin());
+    if (hmax) { depth = 0; for (unsigned v = (unsigned)*hmax + 1; v; v >>= 1) ++depth; }
+    PTV3_REQUIRE(depth >= 1 && depth <= 16, "forward: serialization depth %d outside [1,16] (structure.py:81)", depth);
+    for (int i = 0; i < io->b; ++i)
+      PTV3_REQUIRE(L0.off_host[i] > (i ? L0.off_host[i - 1] : 0), "forward: empty scene %d", i);
+    PTV3_REQUIRE(L0.off_host[io->b - 1] == io->n, "forward: offset does not end at n");
+  }
+  L0.depth = depth;
+  if (io->depth_out) *io->depth_out = depth;
   {
+    // the sort's last pass leaves row_order beside order and inverse
     RUNR(ptv3_sfc_encode(io->grid_coord, io->coord_is_i64, L0.batch, io->n, depth, io->order_ids_host, k, L0.code, sg));
     size_t wsb = ptv3_argsort_workspace_bytes(k, io->n);
     void* ws = G.alloc(wsb);
-    RUNR(ptv3_argsort_i64(L0.code, k, io->n, std::max(1, 3 * depth + nbits), L0.order, L0.inverse, ws, wsb, sg));
+    RUNR(ptv3_argsort_i64_rows(L0.code, k, io->n, std::max(1, 3 * depth + nbits), L0.order, L0.inverse, L0.row_order, ws, wsb,
+                               sg));
   }
-  if (!dry) R.stem_ready = X->event_at(19);
-  R.level_geometry(L0, 0, io->grid_coord, io->coord_is_i64, true);
+  // the stem conv needs the 5^3 table and the row order only: it starts here, under the 3^3 table and the window plans
+  if (!dry && R.ok()) { R.stem_ready = X->event_at(19); (void)hipEventRecord(R.stem_ready, sg); }
+  R.level_tables(L0, 0);
   if (io->stage_points_host) io->stage_points_host[0] = L0.n;
   if (!dry && R.ok()) { L0.ready = X->event_at(1); (void)hipEventRecord(L0.ready, sg); }
 
@@ -527,7 +635,7 @@ static int run_forward(Exec* X, const ptv3_model_desc* d, const void* const* par
         void* ws = G.alloc(wsb);
         RUNR(ptv3_argsort_i64(L.code, k, L.n, std::max(1, 3 * L.depth + nbits), L.order, L.inverse, ws, wsb, sg));
       }
-      R.level_geometry(L, st, L.grid, 1, false);
+      R.level_geometry(L, st, L.grid, 1);
       if (!d->enc_mode) {
         P.cluster32 = (int32_t*)G.alloc((size_t)P.n * 4);
         if (!dry && R.ok())
@@ -639,6 +747,15 @@ static void plan_bytes(const ptv3_model_desc* desc, int64_t n, int b, size_t* ge
 }  // namespace ptv3
 
 using namespace ptv3;
+
+extern "C" int ptv3_coord_max(const void* grid_coord, int coord_is_i64, int64_t n, int32_t* state, int32_t* out_max,
+                              void* stream) {
+  PTV3_REQUIRE(n >= 1 && n < ((int64_t)1 << 31) && grid_coord && state && out_max, "coord_max: n=%lld or a null pointer",
+               (long long)n);
+  coord_max(grid_coord, coord_is_i64, n, state, out_max, nullptr, 0, nullptr, (hipStream_t)stream);
+  PTV3_LAUNCH_CHECK();
+  return PTV3_OK;
+}
 
 extern "C" size_t ptv3_forward_workspace_bytes(const ptv3_model_desc* desc, int64_t n, int b) {
   if (check_desc(desc)) return 0;

@@ -161,23 +161,35 @@ __global__ void __launch_bounds__(256 * RSC_PARTS) radix_scan_kernel(uint32_t* _
 // separate scan launch disappears.  Each block reads nblk*256 counters, so the host only picks this form for
 // nblk <= RS_FUSED_SCAN_MAX_BLOCKS (every level of a 100k-point scene: nblk <= 49).
 constexpr int RS_FUSED_SCAN_MAX_BLOCKS = 128;
+constexpr int RS_SCAN_BATCH = 32;
 
+// row_order (LAST only, may be null): row 0 of `order` once more as int32, the gather order of the sparse convolutions.
 template <bool FIRST, bool LAST, bool SCAN>
 __global__ void __launch_bounds__(RS_THREADS)
 radix_scatter_kernel(const uint64_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
                      uint64_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
-                     int64_t* __restrict__ order, int64_t* __restrict__ inverse, int64_t n, int shift,
-                     const uint32_t* __restrict__ hist, int nblk) {
+                     int64_t* __restrict__ order, int64_t* __restrict__ inverse, int32_t* __restrict__ row_order,
+                     int64_t n, int shift, const uint32_t* __restrict__ hist, int nblk) {
   __shared__ uint32_t cnt[RS_WAVES][256];  // running per-wave digit counts, then wave bases
   __shared__ uint32_t gbase[256];
   __shared__ uint32_t wsum[RS_WAVES];
   if (SCAN) {
     const uint32_t* hr = hist + (int64_t)blockIdx.y * nblk * 256 + threadIdx.x;   // digit = threadIdx.x
+    // RS_SCAN_BATCH counters in flight per round trip, loaded unconditionally: a slot past the last block reads the
+    // last block again and a select drops it (one load and a full wait per block was 25 round trips at nblk = 49)
     uint32_t total = 0, before = 0;
-    for (int b = 0; b < nblk; ++b) {
-      const uint32_t c = hr[(int64_t)b * 256];
-      total += c;
-      if (b < (int)blockIdx.x) before += c;
+    for (int b0 = 0; b0 < nblk; b0 += RS_SCAN_BATCH) {
+      uint32_t v[RS_SCAN_BATCH];
+#pragma unroll
+      for (int u = 0; u < RS_SCAN_BATCH; ++u) v[u] = hr[(int64_t)min(b0 + u, nblk - 1) * 256];
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < RS_SCAN_BATCH; ++u) {
+        const int b = b0 + u;
+        const uint32_t c = b < nblk ? v[u] : 0u;
+        total += c;
+        before += b < (int)blockIdx.x ? c : 0u;
+      }
     }
     uint32_t x = total;
     const int ln = threadIdx.x & 63;
@@ -202,11 +214,15 @@ radix_scatter_kernel(const uint64_t* __restrict__ keys_in, const uint32_t* __res
   const int64_t wbase = (int64_t)blockIdx.x * RS_TILE + (int64_t)wave * (RS_ITEMS * 64);
   uint64_t key[RS_ITEMS];
   uint32_t rank[RS_ITEMS];
+  // the tile's keys in one round trip, from a clamped index (a load behind `if (i < n)` is a branch and a full wait per key)
+#pragma unroll
+  for (int r = 0; r < RS_ITEMS; ++r) key[r] = kin[min(wbase + r * 64 + lane, n - 1)];
+  __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int r = 0; r < RS_ITEMS; ++r) {
     int64_t i = wbase + r * 64 + lane;
     bool valid = i < n;
-    key[r] = valid ? kin[i] : ~0ull;
+    if (!valid) key[r] = ~0ull;
     uint32_t d = valid ? (uint32_t)((key[r] >> shift) & 255) : 256u;
     // lanes of this wave holding the same digit
     uint64_t peers = __ballot(valid);
@@ -239,16 +255,24 @@ radix_scatter_kernel(const uint64_t* __restrict__ keys_in, const uint32_t* __res
   }
   __syncthreads();
   const uint32_t* hrow = hist + ((int64_t)row * nblk + blockIdx.x) * 256;
+  // the tile's values in one round trip as well (behind `if (i < n)` each one was load, wait, store)
+  uint32_t val[RS_ITEMS];
+  if (!FIRST) {
+#pragma unroll
+    for (int r = 0; r < RS_ITEMS; ++r) val[r] = vals_in[(int64_t)row * n + min(wbase + r * 64 + lane, n - 1)];
+    __builtin_amdgcn_sched_barrier(0);
+  }
 #pragma unroll
   for (int r = 0; r < RS_ITEMS; ++r) {
     int64_t i = wbase + r * 64 + lane;
     if (i < n) {
       uint32_t d = (uint32_t)((key[r] >> shift) & 255);
       int64_t pos = (int64_t)(SCAN ? gbase[d] : hrow[d]) + cnt[wave][d] + rank[r];
-      uint32_t v = FIRST ? (uint32_t)i : vals_in[(int64_t)row * n + i];
+      uint32_t v = FIRST ? (uint32_t)i : val[r];
       if (LAST) {
         order[(int64_t)row * n + pos] = (int64_t)v;
         inverse[(int64_t)row * n + v] = pos;
+        if (row_order && row == 0) row_order[pos] = (int32_t)v;
       } else {
         keys_out[(int64_t)row * n + pos] = key[r];
         vals_out[(int64_t)row * n + pos] = v;
@@ -434,8 +458,9 @@ extern "C" size_t ptv3_argsort_workspace_bytes(int k, int64_t n) {
   return 2 * keys + 2 * vals + hist;
 }
 
-extern "C" int ptv3_argsort_i64(const int64_t* code, int k, int64_t n, int end_bit, int64_t* order,
-                                int64_t* inverse, void* workspace, size_t workspace_bytes, void* stream) {
+// row_order: see radix_scatter_kernel
+static int argsort_run(const int64_t* code, int k, int64_t n, int end_bit, int64_t* order, int64_t* inverse,
+                       int32_t* row_order, void* workspace, size_t workspace_bytes, void* stream) {
   PTV3_REQUIRE(end_bit >= 1 && end_bit <= 64, "argsort: end_bit %d outside [1,64]", end_bit);
   PTV3_REQUIRE(n < (1ll << 31), "argsort: n too large");
   PTV3_REQUIRE(workspace_bytes >= ptv3_argsort_workspace_bytes(k, n), "argsort: workspace too small");
@@ -462,9 +487,9 @@ extern "C" int ptv3_argsort_i64(const int64_t* code, int k, int64_t n, int end_b
     uint32_t* vout = vbuf[p & 1];
 #define RS_SCATTER(F, L)                                                                                          \
     if (fused) hipLaunchKernelGGL((radix_scatter_kernel<F, L, true>), grid, block, 0, s, kin, vin, kout, vout, order, \
-                                  inverse, n, shift, hist, nblk);                                                 \
+                                  inverse, row_order, n, shift, hist, nblk);                                      \
     else hipLaunchKernelGGL((radix_scatter_kernel<F, L, false>), grid, block, 0, s, kin, vin, kout, vout, order,  \
-                            inverse, n, shift, hist, nblk)
+                            inverse, row_order, n, shift, hist, nblk)
     if (first && last) { RS_SCATTER(true, true); }
     else if (first) { RS_SCATTER(true, false); }
     else if (last) { RS_SCATTER(false, true); }
@@ -475,6 +500,19 @@ extern "C" int ptv3_argsort_i64(const int64_t* code, int k, int64_t n, int end_b
   }
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
+}
+
+extern "C" int ptv3_argsort_i64(const int64_t* code, int k, int64_t n, int end_bit, int64_t* order,
+                                int64_t* inverse, void* workspace, size_t workspace_bytes, void* stream) {
+  return argsort_run(code, k, n, end_bit, order, inverse, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ptv3_argsort_scan_batch(void) { return RS_SCAN_BATCH; }
+
+extern "C" int ptv3_argsort_i64_rows(const int64_t* code, int k, int64_t n, int end_bit, int64_t* order,
+                                     int64_t* inverse, int32_t* row_order, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  return argsort_run(code, k, n, end_bit, order, inverse, row_order, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ptv3_pad_plan(const int64_t* offset, int b, int64_t n, int64_t n_pad, int patch, int64_t* pad,

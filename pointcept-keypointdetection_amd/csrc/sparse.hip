@@ -109,6 +109,27 @@ static inline BlockTable bt_layout(void* table, int64_t n) {
   return t;
 }
 
+// sites (batch, x, y, z) as int32 from the batch ids and (n, 3) coordinates, the coordinates once more as int64 when
+// grid64 is given, and the zero fill of the block table that will be built over these sites (zero16 x 16 bytes,
+// grid-stride): one launch where a conversion kernel and a memset stood in front of bt_claim_kernel
+__global__ void bt_sites_kernel(const int64_t* __restrict__ batch, const void* __restrict__ grid, int is_i64, int64_t n,
+                                int32_t* __restrict__ idx, int64_t* __restrict__ grid64, uint4* __restrict__ zero,
+                                int64_t zero16) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (int64_t j = i; j < zero16; j += (int64_t)gridDim.x * blockDim.x) zero[j] = uint4{0u, 0u, 0u, 0u};
+  if (i >= n) return;
+  int64_t x, y, z;
+  if (is_i64) {
+    const int64_t* g = (const int64_t*)grid;
+    x = g[3 * i]; y = g[3 * i + 1]; z = g[3 * i + 2];
+  } else {
+    const int32_t* g = (const int32_t*)grid;
+    x = g[3 * i]; y = g[3 * i + 1]; z = g[3 * i + 2];
+  }
+  reinterpret_cast<int4*>(idx)[i] = int4{(int32_t)batch[i], (int32_t)x, (int32_t)y, (int32_t)z};
+  if (grid64) { grid64[3 * i] = x; grid64[3 * i + 1] = y; grid64[3 * i + 2] = z; }
+}
+
 // every site claims its block's slot and sets its voxel's bit; the slot is kept for bt_payload_kernel
 __global__ void bt_claim_kernel(const int32_t* __restrict__ idx, int64_t n, BlockSlot* slots, uint64_t smask,
                                 int32_t* __restrict__ site_slot) {
@@ -301,15 +322,29 @@ extern "C" size_t ptv3_subm_block_table_bytes(int64_t n) {
   return (size_t)ptv3_subm_table_slots(n) * sizeof(BlockSlot) + 2 * bt_payload_bytes(n) + 16;
 }
 
-extern "C" int ptv3_subm_build_block_table(const int32_t* indices, int64_t n, void* table, size_t bytes,
-                                           void* stream) {
+extern "C" int ptv3_subm_sites(const int64_t* batch, const void* grid_coord, int coord_is_i64, int64_t n,
+                               int32_t* indices, int64_t* grid64, void* table, size_t bytes, void* stream) {
+  PTV3_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "subm_sites: n=%lld out of range", (long long)n);
+  PTV3_REQUIRE(table && bytes >= ptv3_subm_block_table_bytes(n) && ((uintptr_t)table & 15) == 0,
+               "subm_sites: table must be 16-byte aligned and hold ptv3_subm_block_table_bytes(n) bytes");
+  PTV3_REQUIRE(n == 0 || (batch && grid_coord && indices), "subm_sites: batch, grid_coord and indices are required");
+  PTV3_REQUIRE(((uintptr_t)indices & 15) == 0, "subm_sites: indices must be 16-byte aligned");
+  const BlockTable t = bt_layout(table, n);
+  hipLaunchKernelGGL(bt_sites_kernel, dim3((unsigned)cdiv(n > 0 ? n : 1, 256)), dim3(256), 0, (hipStream_t)stream, batch,
+                     grid_coord, coord_is_i64, n, indices, grid64, (uint4*)table, (int64_t)(t.zero_bytes / 16));
+  PTV3_LAUNCH_CHECK();
+  return PTV3_OK;
+}
+
+// zeroed: the table's first zero_bytes are already zero on the stream (ptv3_subm_sites)
+static int build_block_table(const int32_t* indices, int64_t n, void* table, size_t bytes, bool zeroed, void* stream) {
   PTV3_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), "subm_build_block_table: n=%lld out of range", (long long)n);
   PTV3_REQUIRE(table && bytes >= ptv3_subm_block_table_bytes(n) && ((uintptr_t)table & 15) == 0,
                "subm_build_block_table: table must be 16-byte aligned and hold ptv3_subm_block_table_bytes(n) bytes");
   PTV3_REQUIRE(n == 0 || indices, "subm_build_block_table: indices are required");
   hipStream_t s = (hipStream_t)stream;
   const BlockTable t = bt_layout(table, n);
-  if (hipMemsetAsync(table, 0, t.zero_bytes, s) != hipSuccess) {
+  if (!zeroed && hipMemsetAsync(table, 0, t.zero_bytes, s) != hipSuccess) {
     set_error("subm_build_block_table: memset failed");
     return PTV3_ERR_LAUNCH;
   }
@@ -320,6 +355,16 @@ extern "C" int ptv3_subm_build_block_table(const int32_t* indices, int64_t n, vo
   hipLaunchKernelGGL(bt_payload_kernel, sites, block, 0, s, indices, n, t.slots, t.site_slot, t.payload);
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
+}
+
+extern "C" int ptv3_subm_build_block_table(const int32_t* indices, int64_t n, void* table, size_t bytes,
+                                           void* stream) {
+  return build_block_table(indices, n, table, bytes, false, stream);
+}
+
+extern "C" int ptv3_subm_build_block_table_zeroed(const int32_t* indices, int64_t n, void* table, size_t bytes,
+                                                  void* stream) {
+  return build_block_table(indices, n, table, bytes, true, stream);
 }
 
 template <int K, int SITES>

@@ -42,6 +42,11 @@ SIGNATURES = {
     "ptv3_sfc_encode": (c_int, [P, c_int, P, c_int64, c_int, P, c_int, P, P]),
     "ptv3_argsort_workspace_bytes": (c_size_t, [c_int, c_int64]),
     "ptv3_argsort_i64": (c_int, [P, c_int, c_int64, c_int, P, P, P, c_size_t, P]),
+    "ptv3_argsort_i64_rows": (c_int, [P, c_int, c_int64, c_int, P, P, P, P, c_size_t, P]),
+    "ptv3_argsort_scan_batch": (c_int, []),
+    "ptv3_coord_max": (c_int, [P, c_int, c_int64, P, P, P]),
+    "ptv3_subm_sites": (c_int, [P, P, c_int, c_int64, P, P, P, c_size_t, P]),
+    "ptv3_subm_build_block_table_zeroed": (c_int, [P, c_int64, P, c_size_t, P]),
     "ptv3_pad_plan": (c_int, [P, c_int, c_int64, c_int64, c_int, P, P, P, P]),
     "ptv3_window_maps": (c_int, [P, P, P, P, c_int64, c_int64, P, P, P]),
     "ptv3_window_plan": (c_int, [P, P, P, c_int, c_int, c_int64, c_int64, c_int, P, P, P, P]),

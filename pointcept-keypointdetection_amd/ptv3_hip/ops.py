@@ -79,6 +79,34 @@ def argsort_codes(code, end_bit):
     return order, inverse
 
 
+def argsort_codes_rows(code, end_bit):
+    """argsort_codes() through ptv3_argsort_i64_rows, the executor's form: (order, inverse, row_order), row_order (n)
+    int32 = order[0], written by the sort's last pass."""
+    _chk(code, "code", torch.int64, 2)
+    k, n = code.shape
+    ws_bytes = lib.ptv3_argsort_workspace_bytes(k, n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=code.device)
+    order = torch.empty_like(code)
+    inverse = torch.empty_like(code)
+    row_order = torch.empty(n, dtype=torch.int32, device=code.device)
+    lib.check(lib.ptv3_argsort_i64_rows(_p(code), k, n, int(end_bit), _p(order), _p(inverse), _p(row_order), _p(ws),
+                                        ws_bytes, _stream()), "ptv3_argsort_i64_rows")
+    return order, inverse, row_order
+
+
+def coord_max(grid_coord, state=None):
+    """max(0, largest grid coordinate) as a (1,) int32 device tensor (the executor's depth read-back).  state: (2,)
+    int32 zeros, left zero again by the kernel (the executor keeps one and never refills it)."""
+    _chk(grid_coord, "grid_coord", (torch.int32, torch.int64), 2)
+    _chk(state, "state", torch.int32, 1)
+    if state is None:
+        state = torch.zeros(2, dtype=torch.int32, device=grid_coord.device)
+    out = torch.empty(1, dtype=torch.int32, device=grid_coord.device)
+    lib.check(lib.ptv3_coord_max(_p(grid_coord), int(grid_coord.dtype == torch.int64), grid_coord.shape[0], _p(state),
+                                 _p(out), _stream()), "ptv3_coord_max")
+    return out
+
+
 def plan_sizes(offset_host, patch):
     """(n_pad, windows, ragged, sum of len^2) of the pad plan (v3m1_base.py:114-170): a scene longer than `patch` is
     padded to a multiple of it, a shorter one stays ONE short window (ragged; only with enable_flash=True)."""
@@ -308,6 +336,22 @@ def subm_neighbors_blocks(indices, ksize, table=None):
     lib.check(lib.ptv3_subm_neighbors_blocks(_p(indices), n, _p(table), table.numel(), int(ksize), _p(nbr), _stream()),
               "ptv3_subm_neighbors_blocks")
     return nbr, table
+
+
+def subm_sites_table(batch, grid_coord):
+    """The executor's level-0 table build: (indices (n,4) int32, grid64 (n,3) int64, table).  One launch writes the
+    sites and zero-fills the table (ptv3_subm_sites), ptv3_subm_build_block_table_zeroed builds it without a memset."""
+    _chk(batch, "batch", torch.int64, 1)
+    _chk(grid_coord, "grid_coord", (torch.int32, torch.int64), 2)
+    n = grid_coord.shape[0]
+    indices = torch.empty((n, 4), dtype=torch.int32, device=batch.device)
+    grid64 = torch.empty((n, 3), dtype=torch.int64, device=batch.device)
+    table = torch.empty(lib.ptv3_subm_block_table_bytes(n), dtype=torch.uint8, device=batch.device)
+    lib.check(lib.ptv3_subm_sites(_p(batch), _p(grid_coord), int(grid_coord.dtype == torch.int64), n, _p(indices),
+                                  _p(grid64), _p(table), table.numel(), _stream()), "ptv3_subm_sites")
+    lib.check(lib.ptv3_subm_build_block_table_zeroed(_p(indices), n, _p(table), table.numel(), _stream()),
+              "ptv3_subm_build_block_table_zeroed")
+    return indices, grid64, table
 
 
 def gemm(x, w, bias=None, nbr=None, kvol=1, row_order=None, bn_scale=None, bn_shift=None, act=ACT_NONE,
