@@ -189,6 +189,31 @@ int ptv3_gemm(const void* x, const void* w, void* out, int64_t m, int cin, int c
               const float* bn_shift, int act, const void* res, const int32_t* res_index, void* out2,
               int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- narrow 3^3 convolution with the tile's neighbour rows held in LDS --------------------------------
+ * ptv3_gemm gathers the rows of x once per tap.  For cin = cout = c in {32, 64} and kvol = 27 the rows a tile of
+ * consecutive sites needs can be fetched once instead: ptv3_halo_plan_build cuts the m sites, in row_order, into tiles
+ * of T sites and lists per tile its distinct neighbour rows (at most CAP), a 16-bit slot into that list for every
+ * (site, tap) (0xFFFF = no neighbour) and the number of distinct rows; ptv3_halo_plan_shape returns (T, CAP).
+ * Plan memory, ptv3_halo_plan_bytes(m) bytes, 16-byte aligned, tiles = ceil(m / T):
+ *   count: tiles x int32, padded to 16 bytes | rows: tiles x CAP x int32 | slots: tiles x T x 27 x uint16
+ * A tile with count > CAP keeps its count and slots, its row list is cut at CAP; ptv3_conv_halo gathers such a tile
+ * per tap from global memory inside the same launch.  The plan depends on nbr and row_order alone: build it once per
+ * level and share it among the level's convolutions.  Nothing is read back to the host.
+ * ptv3_conv_halo: ptv3_gemm(x, w, out, m, c, c, 27, nbr, row_order, ...) with the same epilogue, bitwise the result of
+ * its single-pass 64-point tile in fp32 and bf16 (the same matrix-core chain over taps 0..26, zeros for absent
+ * neighbours).  nbr and row_order must be the ones the plan was built from.
+ * ptv3_conv_halo_policy: 1 where the executor takes ptv3_conv_halo for this shape (PTV3_CONV_HALO = 0 never, 1 the
+ * measured policy, 2 every shape the kernel can run), else 0. */
+size_t ptv3_halo_plan_bytes(int64_t m);
+int ptv3_halo_plan_shape(int* tile_sites, int* cap_rows);
+int ptv3_halo_plan_build(const int32_t* nbr, const int32_t* row_order, int64_t m, void* plan, size_t bytes,
+                         void* stream);
+int ptv3_conv_halo_policy(int64_t m, int cin, int cout, int kvol, int dtype);
+int ptv3_conv_halo(const void* x, const void* w, void* out, int64_t m, int c, const int32_t* nbr,
+                   const int32_t* row_order, const void* plan, size_t plan_bytes, const float* bias,
+                   const float* bn_scale, const float* bn_shift, int act, const void* res, const int32_t* res_index,
+                   void* out2, int dtype, void* stream);
+
 /* ---- fused row-local halves of Block.forward (point_transformer_v3m1_base.py:318-338) ----------------
  * ptv3_block_fusable(c, hidden, dtype, m) names the variant the two entry points below will run:
  *   1  c in {32,64} (the large-M levels): one wave carries 16 points through the whole chain in registers

@@ -134,6 +134,8 @@ struct Level {
   int64_t *code = nullptr, *order = nullptr, *inverse = nullptr;
   int32_t* indices = nullptr; void* table = nullptr; size_t table_bytes = 0;   // table of 4^3 blocks (sparse.hip)
   int32_t* nbr3 = nullptr; int32_t* nbr5 = nullptr; int32_t* row_order = nullptr;
+  // halo plan of nbr3 in row_order (ptv3_halo_plan_build) where a conv of the level takes it; built BEHIND `ready`
+  void* halo = nullptr; size_t halo_bytes = 0; hipEvent_t halo_ready = nullptr; bool halo_waited = false;
   Plan plan[2];                 // [0] encoder patch, [1] decoder patch (shared when K is equal)
   int32_t* seg = nullptr;       // runs of THIS level's points in order 0 that form the next level's rows
   int64_t* cluster = nullptr;   // pooling_inverse: this level's point -> next level's row
@@ -291,6 +293,33 @@ struct Run {
     F->off = mark;  // stream order makes immediate reuse safe
   }
 
+  // One halo plan for the level's narrow convolutions (encoder and decoder blocks).  It is queued on the geometry stream
+  // BEHIND the level's `ready` event, with an event of its own: the feature stream already waits for `ready` when the
+  // level before it ends (level 0: ~50 us after the stem conv), and a kernel in front of `ready` would add its whole
+  // length to that wait.  The first block of the level therefore runs its conv through ptv3_gemm while the plan is
+  // built beside it; the later blocks wait for the plan's event, which has long fired.
+  void halo_plan(Level& L, int st) {
+    const bool dec_here = !d->enc_mode && st < d->num_stages - 1;
+    if (!ptv3_conv_halo_policy(L.n, d->enc_channels[st], d->enc_channels[st], 27, d->dtype) &&
+        !(dec_here && ptv3_conv_halo_policy(L.n, d->dec_channels[st], d->dec_channels[st], 27, d->dtype)))
+      return;
+    L.halo_bytes = ptv3_halo_plan_bytes(L.n);
+    L.halo = G->alloc(L.halo_bytes);
+    RUN(ptv3_halo_plan_build(L.nbr3, L.row_order, L.n, L.halo, L.halo_bytes, sg));
+    if (!dry && ok()) { L.halo_ready = X->event_at(40 + st); (void)hipEventRecord(L.halo_ready, sg); }
+  }
+
+  // the single-pass 3^3 conv of a block: the halo tile where the level has a plan and the policy takes the shape
+  void conv3(Level& L, const void* w, void* out, int C, const float* bias, bool first_block) {
+    if (L.halo && !first_block && ptv3_conv_halo_policy(L.n, C, C, 27, d->dtype)) {
+      if (!dry && ok() && !L.halo_waited) { (void)hipStreamWaitEvent(sf, L.halo_ready, 0); L.halo_waited = true; }
+      RUN(ptv3_conv_halo(L.conv_feat, w, out, L.n, C, L.nbr3, L.row_order, L.halo, L.halo_bytes, bias, nullptr, nullptr, 0,
+                         nullptr, nullptr, nullptr, d->dtype, sf));
+      return;
+    }
+    gemm(L.conv_feat, w, out, L.n, C, C, 27, L.nbr3, L.row_order, bias, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
+  }
+
   // whole-row linears (ptv3_rows_linear) instead of LayerNorm + tiled GEMM launches: measured ahead at 245 .. 1388 rows
   // (column groups) and at 27 743+ rows alike (tools/bench_block_wide.py); PTV3_ROWS_MIN raises the row count it starts at
   bool rows_path(int64_t n, int C, int hidden) const {
@@ -386,7 +415,7 @@ struct Run {
   }
 
   // Block.forward (:318-338), eval, pre_norm; cpe Linear folded into the conv taps
-  void block(Level& L, const Plan& P, int C, int H, int oi) {
+  void block(Level& L, const Plan& P, int C, int H, int oi, bool first = false) {
     const void* conv_w = next(); const float* conv_b = (const float*)next();
     const float* ln0_g = (const float*)next(); const float* ln0_b = (const float*)next();
     const float* n1_g = (const float*)next(); const float* n1_b = (const float*)next();
@@ -412,7 +441,7 @@ struct Run {
                             C, d->ln_eps, d->dtype, sf));
       } else {
         void* t2 = F->alloc(row * C);
-        gemm(L.conv_feat, conv_w, t2, L.n, C, C, 27, L.nbr3, L.row_order, conv_b, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
+        conv3(L, conv_w, t2, C, conv_b, first);
         RUN(ptv3_block_head(t2, nullptr, 0, nullptr, L.feat, ln0_g, ln0_b, n1_g, n1_b, qkv_w, qkv_b, f1, qkv, L.n, C,
                             d->ln_eps, d->dtype, sf));
       }
@@ -436,11 +465,11 @@ struct Run {
                                  d->dtype, sf));
         gemm(t3, qkv_w, qkv, L.n, C, 3 * C, 1, nullptr, nullptr, qkv_b, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
       } else if (rows) {
-        gemm(L.conv_feat, conv_w, t2, L.n, C, C, 27, L.nbr3, L.row_order, conv_b, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
+        conv3(L, conv_w, t2, C, conv_b, first);
         RUN(ptv3_rows_linear(t2, L.feat, ln0_g, ln0_b, n1_g, n1_b, qkv_w, qkv_b, 0, nullptr, f1, qkv, L.n, C, 3 * C,
                              d->ln_eps, d->dtype, sf));
       } else {
-        gemm(L.conv_feat, conv_w, t2, L.n, C, C, 27, L.nbr3, L.row_order, conv_b, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
+        conv3(L, conv_w, t2, C, conv_b, first);
         RUN(ptv3_layernorm(t2, ln0_g, ln0_b, L.feat, f1, n1_g, n1_b, t3, L.n, C, d->ln_eps, d->dtype, sf));
         gemm(t3, qkv_w, qkv, L.n, C, 3 * C, 1, nullptr, nullptr, qkv_b, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
       }
@@ -571,6 +600,7 @@ static int run_forward(Exec* X, const ptv3_model_desc* d, const void* const* par
   R.level_tables(L0, 0);
   if (io->stage_points_host) io->stage_points_host[0] = L0.n;
   if (!dry && R.ok()) { L0.ready = X->event_at(1); (void)hipEventRecord(L0.ready, sg); }
+  R.halo_plan(L0, 0);
 
   // ---------------- features of level 0 start as soon as its geometry is queued
   auto wait_level = [&](Level& L) { if (!dry && R.ok()) (void)hipStreamWaitEvent(sf, L.ready, 0); };
@@ -642,6 +672,7 @@ static int run_forward(Exec* X, const ptv3_model_desc* d, const void* const* par
           hipLaunchKernelGGL(i64_to_i32_kernel, dim3((unsigned)cdiv(P.n, 256)), dim3(256), 0, sg, P.cluster, P.cluster32, P.n);
       }
       if (!dry && R.ok()) { L.ready = X->event_at(1 + st); (void)hipEventRecord(L.ready, sg); }
+      R.halo_plan(L, st);
       // ---- features of the pooled level: proj -> segmented max + folded BN + GELU (:416-418, 439-442)
       wait_level(L);
       L.feat = F.alloc((size_t)L.n * C * es);
@@ -654,7 +685,7 @@ static int run_forward(Exec* X, const ptv3_model_desc* d, const void* const* par
       L.conv_feat = L.feat;
     }
     for (int i = 0; i < d->enc_depths[st]; ++i)
-      R.block(L, L.plan[0], d->enc_channels[st], d->enc_heads[st], i % k);
+      R.block(L, L.plan[0], d->enc_channels[st], d->enc_heads[st], i % k, i == 0);
     if (!R.ok()) break;
   }
   // ---------------- decoder (:651-697)

@@ -4,6 +4,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "hashtable.h"
+#include "halo_plan.h"
 #include "../../include/ptv3_hip.h"
 
 namespace ptv3 {
@@ -261,6 +262,87 @@ __global__ __launch_bounds__(256) void bt_neighbors_kernel(const int32_t* __rest
   }
 }
 
+// ---- halo plan (halo_plan.h) -------------------------------------------------------------------------------------
+// One workgroup per tile of HALO_T sites: the tile's 128 x 27 table entries are de-duplicated in an LDS hash
+// (compare-and-swap, linear probing: at most 3456 keys in 4096 cells), the occupied cells are numbered by a prefix sum
+// over the cells - so the numbering depends on the keys alone, not on which lane won a cell - and every (site, tap)
+// gets the number of its row's cell.  Nothing is read back: the count stays on the device for the convolution.
+constexpr int HALO_HASH = 4096;
+__global__ __launch_bounds__(256) void halo_plan_kernel(const int32_t* __restrict__ nbr,
+                                                        const int32_t* __restrict__ row_order, int64_t n, HaloPlan p) {
+  constexpr int ENT = HALO_T * HALO_TAPS, PER = (ENT + 255) / 256, CELLS = HALO_HASH / 256;
+  __shared__ int32_t s_key[HALO_HASH];
+  __shared__ uint16_t s_slot[HALO_HASH];
+  __shared__ int s_wave[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t tile = blockIdx.x, row0 = tile * HALO_T;
+  for (int c = tid; c < HALO_HASH; c += 256) s_key[c] = -1;
+  // entry e = tid + 256 u of the tile's table: all row lookups, then all table reads, in flight together
+  int64_t orow[PER];
+  bool in[PER];
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int e = tid + 256 * u;
+    const int64_t r = row0 + e / HALO_TAPS;
+    in[u] = e < ENT && r < n;
+    const int64_t rs = in[u] ? r : 0;
+    orow[u] = row_order ? (int64_t)row_order[rs] : rs;
+  }
+  int32_t v[PER];
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int e = tid + 256 * u;
+    v[u] = nbr[orow[u] * HALO_TAPS + e % HALO_TAPS];
+    if (!in[u]) v[u] = -1;
+  }
+  __syncthreads();
+  int cell[PER];
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    cell[u] = -1;
+    if (v[u] < 0) continue;
+    unsigned hsh = ((unsigned)v[u] * 2654435761u) >> 20;   // 12 bits
+    for (int probe = 0; probe < HALO_HASH; ++probe) {
+      // most entries repeat a row another site has inserted already (16 present taps per site, 2 distinct rows): a
+      // plain read finds those without a compare-and-swap on a contended cell
+      int32_t prev = *(volatile int32_t*)&s_key[hsh];
+      if (prev == -1) prev = atomicCAS(&s_key[hsh], -1, v[u]);
+      if (prev == -1 || prev == v[u]) { cell[u] = (int)hsh; break; }
+      hsh = (hsh + 1) & (HALO_HASH - 1);
+    }
+  }
+  __syncthreads();
+  // thread t owns cells t, t + 256, ...; slots are numbered thread-major
+  int mine = 0;
+#pragma unroll
+  for (int j = 0; j < CELLS; ++j) mine += s_key[tid + 256 * j] >= 0;
+  int incl = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int up = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int at = incl - mine;
+  for (int wv = 0; wv < wave; ++wv) at += s_wave[wv];
+#pragma unroll
+  for (int j = 0; j < CELLS; ++j) {
+    const int32_t key = s_key[tid + 256 * j];
+    if (key < 0) continue;
+    s_slot[tid + 256 * j] = (uint16_t)at;                    // at < 3456 < HALO_ABSENT
+    if (at < HALO_CAP) p.rows[tile * HALO_CAP + at] = key;
+    ++at;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < PER; ++u) {
+    const int e = tid + 256 * u;
+    if (e < ENT) p.slots[tile * ENT + e] = cell[u] >= 0 ? s_slot[cell[u]] : (uint16_t)HALO_ABSENT;
+  }
+  if (tid == 0) p.count[tile] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+}
+
 }  // namespace ptv3
 
 using namespace ptv3;
@@ -392,6 +474,27 @@ extern "C" int ptv3_subm_neighbors_blocks(const int32_t* indices, int64_t n, con
     case 5: bt_neighbors_launch<5, 16>(indices, n, t, nbr, s); break;
     default: bt_neighbors_launch<7, 4>(indices, n, t, nbr, s); break;
   }
+  PTV3_LAUNCH_CHECK();
+  return PTV3_OK;
+}
+
+extern "C" size_t ptv3_halo_plan_bytes(int64_t m) { return halo_plan_bytes(m); }
+
+extern "C" int ptv3_halo_plan_shape(int* tile_sites, int* cap_rows) {
+  if (tile_sites) *tile_sites = HALO_T;
+  if (cap_rows) *cap_rows = HALO_CAP;
+  return PTV3_OK;
+}
+
+extern "C" int ptv3_halo_plan_build(const int32_t* nbr, const int32_t* row_order, int64_t m, void* plan, size_t bytes,
+                                    void* stream) {
+  PTV3_REQUIRE(m >= 0 && m < ((int64_t)1 << 31), "halo_plan_build: m=%lld out of range", (long long)m);
+  if (m == 0) return PTV3_OK;
+  PTV3_REQUIRE(nbr != nullptr, "halo_plan_build: the 27-tap neighbour table is required");
+  PTV3_REQUIRE(plan && bytes >= halo_plan_bytes(m) && ((uintptr_t)plan & 15) == 0,
+               "halo_plan_build: plan must be 16-byte aligned and hold ptv3_halo_plan_bytes(m) bytes");
+  const HaloPlan p = halo_layout(plan, m);
+  hipLaunchKernelGGL(halo_plan_kernel, dim3((unsigned)p.tiles), dim3(256), 0, (hipStream_t)stream, nbr, row_order, m, p);
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }

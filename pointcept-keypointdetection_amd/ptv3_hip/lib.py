@@ -65,6 +65,11 @@ SIGNATURES = {
     "ptv3_gemm": (c_int, [P, P, P, c_int64, c_int, c_int, c_int, P, P, P, P, P, c_int, P, P, P, c_int, P, c_size_t,
                           P]),
     "ptv3_gemm_splits": (c_int, [c_int64, c_int, c_int, c_int, c_int]),
+    "ptv3_halo_plan_bytes": (c_size_t, [c_int64]),
+    "ptv3_halo_plan_shape": (c_int, [P, P]),
+    "ptv3_halo_plan_build": (c_int, [P, P, c_int64, P, c_size_t, P]),
+    "ptv3_conv_halo_policy": (c_int, [c_int64, c_int, c_int, c_int, c_int]),
+    "ptv3_conv_halo": (c_int, [P, P, P, c_int64, c_int, P, P, P, c_size_t, P, P, P, c_int, P, P, P, c_int, P]),
     "ptv3_block_fusable": (c_int, [c_int, c_int, c_int, c_int64]),
     "ptv3_rows_linear_capable": (c_int, [c_int, c_int, c_int, c_int64]),
     "ptv3_rows_linear": (c_int, [P, P, P, P, P, P, P, P, c_int, P, P, P, c_int64, c_int, c_int, c_float, c_int, P]),

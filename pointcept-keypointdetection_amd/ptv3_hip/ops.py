@@ -396,6 +396,85 @@ def gemm(x, w, bias=None, nbr=None, kvol=1, row_order=None, bn_scale=None, bn_sh
     return (out, out2) if dual else out
 
 
+def halo_plan_shape():
+    """(T, CAP): sites per tile and the most distinct neighbour rows a tile may have on the fast path."""
+    t, cap = ctypes.c_int(0), ctypes.c_int(0)
+    lib.check(lib.ptv3_halo_plan_shape(ctypes.byref(t), ctypes.byref(cap)), "ptv3_halo_plan_shape")
+    return t.value, cap.value
+
+
+def halo_plan(nbr, row_order=None):
+    """Halo plan of a 27-tap neighbour table (ptv3_halo_plan_build): (plan, counts, rows, slots).
+
+    plan is the opaque byte tensor conv_halo takes; the other three are views into it: counts (tiles,) int32 distinct
+    neighbour rows per tile of T consecutive sites of row_order (> CAP: the tile takes the slow path), rows (tiles, CAP)
+    int32 of which the first min(count, CAP) per tile are written, slots (tiles, T, 27) int16 with -1 (0xFFFF) = absent."""
+    _chk(nbr, "nbr", torch.int32, 2)
+    _chk(row_order, "row_order", torch.int32, 1)
+    m = nbr.shape[0]
+    if nbr.shape[1] != 27:
+        raise RuntimeError("halo_plan: the neighbour table must have 27 taps")
+    if row_order is not None and row_order.shape[0] != m:
+        raise RuntimeError("halo_plan: row_order length != m")
+    t, cap = halo_plan_shape()
+    tiles = (m + t - 1) // t
+    nbytes = lib.ptv3_halo_plan_bytes(m)
+    plan = torch.empty(nbytes, dtype=torch.uint8, device=nbr.device)
+    lib.check(lib.ptv3_halo_plan_build(_p(nbr), _p(row_order), m, _p(plan), nbytes, _stream()), "ptv3_halo_plan_build")
+    cb = (tiles * 4 + 15) // 16 * 16
+    rb = tiles * cap * 4
+    counts = plan[:tiles * 4].view(torch.int32)
+    rows = plan[cb:cb + rb].view(torch.int32).view(tiles, cap)
+    slots = plan[cb + rb:cb + rb + tiles * t * 27 * 2].view(torch.int16).view(tiles, t, 27)
+    return plan, counts, rows, slots
+
+
+def conv_halo_policy(m, c, dtype):
+    """Whether the executor runs the c -> c 3^3 conv of m rows through conv_halo (PTV3_CONV_HALO)."""
+    return bool(lib.ptv3_conv_halo_policy(int(m), int(c), int(c), 27, _DT[dtype]))
+
+
+def conv_halo(x, w, nbr, plan, bias=None, row_order=None, bn_scale=None, bn_shift=None, act=ACT_NONE, res=None,
+              res_index=None, dual=False, out=None):
+    """gemm(x, w, nbr=nbr, kvol=27, ...) for cin = cout in {32, 64} with the tile's neighbour rows held in LDS
+    (ptv3_conv_halo); plan = halo_plan(nbr, row_order)[0].  Bitwise the result of the single-pass 64-point tile.
+    out: an (m, c) tensor to write into (tests pre-fill it to see a skipped store)."""
+    _chk(x, "x", (torch.float32, torch.bfloat16), 2)
+    _chk(w, "w", x.dtype)
+    for t, nm in ((bias, "bias"), (bn_scale, "bn_scale"), (bn_shift, "bn_shift")):
+        _chk(t, nm, torch.float32, 1)
+    _chk(nbr, "nbr", torch.int32, 2)
+    _chk(row_order, "row_order", torch.int32, 1)
+    _chk(res, "res", x.dtype, 2)
+    _chk(res_index, "res_index", torch.int32, 1)
+    _chk(plan, "plan", torch.uint8, 1)
+    m, c = nbr.shape[0], x.shape[1]
+    if nbr.shape[1] != 27 or x.shape[0] != m:
+        raise RuntimeError("conv_halo: x must have one row per row of the 27-tap neighbour table")
+    if w.numel() != c * 27 * c:
+        raise RuntimeError(f"conv_halo: weight has {w.numel()} elements, expected {c}x27x{c}")
+    for t in (bias, bn_scale, bn_shift):
+        if t is not None and t.numel() != c:
+            raise RuntimeError("conv_halo: epilogue vector length != c")
+    if res is not None:
+        if res.shape[1] != c or (res_index is None and res.shape[0] != m):
+            raise RuntimeError("conv_halo: residual shape mismatch")
+        if res_index is not None and res_index.shape[0] != m:
+            raise RuntimeError("conv_halo: res_index length != m")
+    if row_order is not None and row_order.shape[0] != m:
+        raise RuntimeError("conv_halo: row_order length != m")
+    if out is None:
+        out = torch.empty((m, c), dtype=x.dtype, device=x.device)
+    _chk(out, "out", x.dtype, 2)
+    if tuple(out.shape) != (m, c):
+        raise RuntimeError("conv_halo: out shape mismatch")
+    out2 = torch.empty_like(out) if dual else None
+    lib.check(lib.ptv3_conv_halo(_p(x), _p(w), _p(out), m, c, _p(nbr), _p(row_order), _p(plan), plan.numel(), _p(bias),
+                                 _p(bn_scale), _p(bn_shift), int(act), _p(res), _p(res_index), _p(out2), _dt(x),
+                                 _stream()), "ptv3_conv_halo")
+    return (out, out2) if dual else out
+
+
 def gemm_splits(m, cin, cout, kvol, dtype):
     """K slabs ptv3_gemm splits the shape into (1: a single pass)."""
     return int(lib.ptv3_gemm_splits(int(m), int(cin), int(cout), int(kvol), _DT[dtype]))
