@@ -213,6 +213,18 @@ int ptv3_conv_halo(const void* x, const void* w, void* out, int64_t m, int c, co
                    const int32_t* row_order, const void* plan, size_t plan_bytes, const float* bias,
                    const float* bn_scale, const float* bn_shift, int act, const void* res, const int32_t* res_index,
                    void* out2, int dtype, void* stream);
+/* ptv3_conv_head_halo: ptv3_conv_halo(x, w, t, m, c, nbr, row_order, plan, plan_bytes, conv_bias, ...) followed by
+ * ptv3_block_head(t, NULL, 0, NULL, shortcut, g0, b0, g1, b1, wqkv, bqkv, f1, qkv, m, c, eps, ...) as one launch that
+ * never writes t: the conv's accumulators are the head's input registers.  f1 and qkv are bitwise those of the two
+ * calls, in fp32 and bf16; wqkv is the chain-permuted weight ptv3_block_head takes at c in {32, 64}.  shortcut may be x.
+ * ptv3_conv_head_halo_policy: 1 where the executor takes it for a block of m rows (PTV3_CONV_HEAD = 0 never, 1 the
+ * measured policy: bf16, c = 64 and m >= a row bound that PTV3_CONV_HEAD_MIN_ROWS overrides, 2 every shape the kernel can
+ * run), else 0. */
+int ptv3_conv_head_halo_policy(int64_t m, int c, int dtype);
+int ptv3_conv_head_halo(const void* x, const void* w, const float* conv_bias, int64_t m, int c, const int32_t* nbr,
+                        const int32_t* row_order, const void* plan, size_t plan_bytes, const void* shortcut,
+                        const float* g0, const float* b0, const float* g1, const float* b1, const void* wqkv,
+                        const float* bqkv, void* f1, void* qkv, float eps, int dtype, void* stream);
 
 /* ---- fused row-local halves of Block.forward (point_transformer_v3m1_base.py:318-338) ----------------
  * ptv3_block_fusable(c, hidden, dtype, m) names the variant the two entry points below will run:

@@ -1,6 +1,7 @@
 // Argument blocks and register-chain helpers shared by the fused halves of Block.forward
 // (block_fused.hip: wave-local / cooperative variants; block_wide.hip: the LDS-DMA weight-streaming variant).
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace ptv3 {
@@ -62,6 +63,48 @@ __device__ __forceinline__ void row_norm(const f32x4* v, float eps, float& mean,
 #pragma unroll
     for (int r = 0; r < 4; ++r) { float d = v[j][r] - mean; q += d * d; }
   rstd = rsqrtf(groups_sum(q) * (1.0f / (16 * NT)) + eps);
+}
+
+// elements of padding behind a weight row in LDS (16 bytes: rows 16 apart land in different banks)
+template <typename T> struct WPad { static constexpr int V = 16 / sizeof(T); };
+
+// Copies a rows x cols matrix into LDS rows of stride ld.  A thread fetches a batch of 16-byte chunks before its first
+// LDS write: one chunk per iteration is `load; s_waitcnt vmcnt(0); ds_write`, a memory round trip per chunk (DESIGN §0
+// rule 6).  A slot past the end copies the last chunk once more (the same bytes to the same place): with a branch
+// around the write the compiler sinks the load into it, and a load behind a branch waits for vmcnt(0) (rule 2).
+template <typename T>
+__device__ __forceinline__ void stage_matrix(T* dst, const T* __restrict__ src, int rows, int cols, int ld) {
+  typedef typename Frag<T>::type FR;
+  constexpr int E = Frag<T>::E;
+  const int cpr = cols / E, total = rows * cpr, nthreads = blockDim.x;
+  auto stage_pass = [&](const int u0, auto unroll_tag) {
+    constexpr int U = decltype(unroll_tag)::value;
+    FR reg[U];
+    int to[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int i = u0 + u * nthreads < total ? u0 + u * nthreads : total - 1;
+      to[u] = (i / cpr) * ld + E * (i % cpr);
+      reg[u] = *reinterpret_cast<const FR*>(src + (unsigned)(E * i));   // the source is dense: chunk i starts at E * i
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) *reinterpret_cast<FR*>(dst + to[u]) = reg[u];
+  };
+  // every thread runs every pass (the caller's barrier follows): 8 chunks each while more than 4 remain per thread
+  int base = 0;
+  for (; base + 4 * nthreads < total; base += 8 * nthreads) stage_pass(base + threadIdx.x, std::integral_constant<int, 8>{});
+  for (; base + nthreads < total; base += 4 * nthreads) stage_pass(base + threadIdx.x, std::integral_constant<int, 4>{});
+  if (base < total) stage_pass(base + threadIdx.x, std::integral_constant<int, 1>{});
+}
+
+// A per-channel vector goes to LDS in two steps: vec_fetch before the weight matrices are staged (element threadIdx.x,
+// clamped: n <= blockDim.x for all but a wide hidden bias), vec_put after them - its round trip is then the matrices'.
+__device__ __forceinline__ float vec_fetch(const float* __restrict__ src, int n) {
+  return src[(int)threadIdx.x < n ? (int)threadIdx.x : n - 1];
+}
+__device__ __forceinline__ void vec_put(float* dst, float v, const float* __restrict__ src, int n) {
+  if ((int)threadIdx.x < n) dst[threadIdx.x] = v;
+  for (int i = threadIdx.x + blockDim.x; i < n; i += blockDim.x) dst[i] = src[i];
 }
 
 // block_wide.hip: the weight-streaming variant for c in {128, 256} at large m

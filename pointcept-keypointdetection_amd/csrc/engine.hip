@@ -300,9 +300,11 @@ struct Run {
   // built beside it; the later blocks wait for the plan's event, which has long fired.
   void halo_plan(Level& L, int st) {
     const bool dec_here = !d->enc_mode && st < d->num_stages - 1;
-    if (!ptv3_conv_halo_policy(L.n, d->enc_channels[st], d->enc_channels[st], 27, d->dtype) &&
-        !(dec_here && ptv3_conv_halo_policy(L.n, d->dec_channels[st], d->dec_channels[st], 27, d->dtype)))
-      return;
+    auto takes = [&](int C) {
+      return ptv3_conv_halo_policy(L.n, C, C, 27, d->dtype) ||
+             (ptv3_conv_head_halo_policy(L.n, C, d->dtype) && ptv3_block_fusable(C, (int)(C * d->mlp_ratio), d->dtype, L.n));
+    };
+    if (!takes(d->enc_channels[st]) && !(dec_here && takes(d->dec_channels[st]))) return;
     L.halo_bytes = ptv3_halo_plan_bytes(L.n);
     L.halo = G->alloc(L.halo_bytes);
     RUN(ptv3_halo_plan_build(L.nbr3, L.row_order, L.n, L.halo, L.halo_bytes, sg));
@@ -432,7 +434,12 @@ struct Run {
       // conv -> [LN + shortcut + LN + qkv] -> window attention -> [proj + shortcut + LN + fc1 + GELU + fc2 + shortcut]
       void* f1 = F->alloc(row * C); void* qkv = F->alloc(row * 3 * C); void* t4 = F->alloc(row * C);
       const int splits = ptv3_gemm_splits(L.n, C, C, 27, d->dtype);
-      if (splits > 1) {
+      if (L.halo && !first && ptv3_conv_head_halo_policy(L.n, C, d->dtype)) {
+        // conv and head in one launch (conv_head.hip): neither the conv output nor split-K slabs exist
+        if (!dry && ok() && !L.halo_waited) { (void)hipStreamWaitEvent(sf, L.halo_ready, 0); L.halo_waited = true; }
+        RUN(ptv3_conv_head_halo(L.conv_feat, conv_w, conv_b, L.n, C, L.nbr3, L.row_order, L.halo, L.halo_bytes, L.feat,
+                                ln0_g, ln0_b, n1_g, n1_b, qkv_w, qkv_b, f1, qkv, d->ln_eps, d->dtype, sf));
+      } else if (splits > 1) {
         const size_t wsb = ptv3_gemm_workspace_bytes(L.n, C, C, 27, d->dtype);
         float* slab = (float*)F->alloc(wsb);
         RUN(ptv3_gemm(L.conv_feat, conv_w, nullptr, L.n, C, C, 27, L.nbr3, L.row_order, nullptr, nullptr, nullptr, 0,

@@ -475,6 +475,42 @@ def conv_halo(x, w, nbr, plan, bias=None, row_order=None, bn_scale=None, bn_shif
     return (out, out2) if dual else out
 
 
+def conv_head_halo_policy(m, c, dtype):
+    """Whether the executor runs the 3^3 conv and the head of a c-channel block of m rows as one kernel
+    (PTV3_CONV_HEAD, PTV3_CONV_HEAD_MIN_ROWS)."""
+    return bool(lib.ptv3_conv_head_halo_policy(int(m), int(c), _DT[dtype]))
+
+
+def conv_head_halo(x, w, conv_bias, nbr, plan, shortcut, g0, b0, g1, b1, wqkv, bqkv, eps, row_order=None):
+    """f1, qkv of conv_halo(x, w, nbr, plan, bias=conv_bias, row_order=row_order) followed by block_head, in one launch
+    (ptv3_conv_head_halo) and bitwise their result; wqkv is chain_permute'd."""
+    _chk(x, "x", (torch.float32, torch.bfloat16), 2)
+    _chk(w, "w", x.dtype)
+    _chk(shortcut, "shortcut", x.dtype, 2)
+    _chk(wqkv, "wqkv", x.dtype, 2)
+    for t, nm in ((conv_bias, "conv_bias"), (g0, "g0"), (b0, "b0"), (g1, "g1"), (b1, "b1"), (bqkv, "bqkv")):
+        _chk(t, nm, torch.float32, 1)
+    _chk(nbr, "nbr", torch.int32, 2)
+    _chk(row_order, "row_order", torch.int32, 1)
+    _chk(plan, "plan", torch.uint8, 1)
+    m, c = nbr.shape[0], x.shape[1]
+    if nbr.shape[1] != 27 or x.shape[0] != m or tuple(shortcut.shape) != (m, c):
+        raise RuntimeError("conv_head_halo: x and shortcut must have one row per row of the 27-tap neighbour table")
+    if w.numel() != c * 27 * c or tuple(wqkv.shape) != (3 * c, c):
+        raise RuntimeError(f"conv_head_halo: weights must be {c}x27x{c} and {3 * c}x{c}")
+    for t, n in ((conv_bias, c), (g0, c), (b0, c), (g1, c), (b1, c), (bqkv, 3 * c)):
+        if t is None or t.numel() != n:
+            raise RuntimeError("conv_head_halo: per-channel vector missing or of the wrong length")
+    if row_order is not None and row_order.shape[0] != m:
+        raise RuntimeError("conv_head_halo: row_order length != m")
+    f1 = torch.empty_like(shortcut)
+    qkv = torch.empty((m, 3 * c), dtype=x.dtype, device=x.device)
+    lib.check(lib.ptv3_conv_head_halo(_p(x), _p(w), _p(conv_bias), m, c, _p(nbr), _p(row_order), _p(plan), plan.numel(),
+                                      _p(shortcut), _p(g0), _p(b0), _p(g1), _p(b1), _p(wqkv), _p(bqkv), _p(f1), _p(qkv),
+                                      float(eps), _dt(x), _stream()), "ptv3_conv_head_halo")
+    return f1, qkv
+
+
 def gemm_splits(m, cin, cout, kvol, dtype):
     """K slabs ptv3_gemm splits the shape into (1: a single pass)."""
     return int(lib.ptv3_gemm_splits(int(m), int(cin), int(cout), int(kvol), _DT[dtype]))

@@ -9,6 +9,10 @@ def label(name):
     if m:
         return "gemm_big_kernel<%s,%sch> %s" % ("bf16" if m.group(1) == "DF16b" else "f32", m.group(4),
                                                  "gather (sparse conv)" if m.group(5) == "1" else "dense")
+    m = re.search(r"conv_head_halo_kernel(?:I(DF16b|f)Li(\d+)E|<(float|__bf16), (\d+)>)", n)
+    if m:
+        return "conv_head_halo_kernel<%s,%sch> (sparse conv + block head)" % (
+            "f32" if (m.group(1) or m.group(3)) in ("f", "float") else "bf16", m.group(2) or m.group(4))
     m = re.search(r"conv_halo_kernel(?:I(DF16b|f)Li(\d+)E|<(float|__bf16), (\d+)>)", n)
     if m:
         return "conv_halo_kernel<%s,%sch> (sparse conv)" % ("f32" if (m.group(1) or m.group(3)) in ("f", "float") else "bf16",
