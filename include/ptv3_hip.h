@@ -270,6 +270,23 @@ int ptv3_mlp2(const void* x, const void* w1, const float* b1, const float* s1, c
 int ptv3_block_tail(const void* attn, const void* f1, const void* wproj, const float* bproj, const float* g2,
                     const float* b2, const void* w1, const float* bias1, const void* w2, const float* bias2,
                     void* out, int64_t m, int c, int hidden, float eps, int dtype, void* stream);
+/* The same tail for few rows (csrc/block_wide.hip, block_tail_sliced_kernel): bf16, c = 128 or 256, hidden = 4 c,
+ * weights in natural layout, 64 rows per workgroup.  The hidden layer is cut across `groups` workgroups per row tile
+ * (groups divides hidden / 64, at most 16); every group leaves an fp32 partial of `out` in `workspace` ([groups][m][c], 16-byte aligned) and a second
+ * launch sums the partials in group order, so the result does not depend on the order the groups finish in.
+ * groups = 1 writes `out` directly, bitwise what ptv3_block_tail's streaming kernel writes, and needs no workspace;
+ * groups = 0 takes ptv3_block_tail_sliced_policy's count.
+ * ptv3_block_tail_sliced_policy: the group count with which the executor takes this tail for a block of m rows, 0
+ * where it does not (PTV3_TAIL_SLICED = 0 never, 1 the measured policy: c = 256 from 245 to 4 096 rows, in place
+ * of two ptv3_rows_linear and a split-K ptv3_gemm, and c = 128 from 5 590 to 16 384 rows with one group, in place of the
+ * cooperative ptv3_block_tail; 2 every m the kernel can run below the rows from which ptv3_block_fusable answers 3;
+ * PTV3_TAIL_SLICED_GROUPS names the count). */
+int ptv3_block_tail_sliced_policy(int c, int hidden, int dtype, int64_t m);
+size_t ptv3_block_tail_sliced_workspace_bytes(int64_t m, int c, int groups);
+int ptv3_block_tail_sliced(const void* attn, const void* f1, const void* wproj, const float* bproj, const float* g2,
+                           const float* b2, const void* w1, const float* bias1, const void* w2, const float* bias2,
+                           void* out, int64_t m, int c, int hidden, float eps, int dtype, int groups, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* ---- bottleneck xCPE of PT-v3m1-Plus (pointcept/models/keypoint_ptv3_plus.py:68-94; csrc/cpe_plus.hip) ----------
  * ptv3_rows_linear_ln: cpe[0..2] = SubMConv3d(C, mid, 1, bias=False) -> LayerNorm(mid) -> ReLU (:70-72) in one launch:

@@ -408,6 +408,227 @@ __global__ void __launch_bounds__(256, WGS) block_tail_wide_kernel(TailArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// The same tail for FEW rows (C = 256 on the ~10^3-row levels of a 100k-point scene, C = 128 on its 5 590-row level),
+// where 128 rows per workgroup leave a dozen workgroups that each walk all NPU + 2 NS weight units alone.  The hidden layer is cut across
+// gridDim.y GROUPS instead: workgroup (row tile x, group y) runs proj + shortcut + LayerNorm for its rows (redundant
+// across the groups, but NPU units only), then the NS / gridDim.y hidden slices from y NS / gridDim.y on through
+// fc1 -> GELU -> fc2, and leaves an fp32 partial of `out` in slab y of `ws` ([gridDim.y][m][C]; group 0 adds
+// bias2 + f2).  tail_sliced_finish_kernel sums the slabs in slab order.  SLAB = false (one group): the epilogue of
+// block_tail_wide_kernel, straight to `out` - bitwise that kernel's result.
+// A partial leaves as fp32: two accumulator tiles side by side are 32 consecutive channels (ChMap<bf16>) = one
+// 128-byte row piece through the same wave-private stage; the pieces are fetched from LDS first, then stored.
+template <int RT>
+__device__ __forceinline__ void wave_store_slab(char* stage, const f32x4 (&v)[RT][2], __amdgpu_buffer_rsrc_t rs,
+                                                int64_t ld, int col0, int64_t base, int li, int g, int lane) {
+#pragma unroll
+  for (int t = 0; t < RT; ++t)
+#pragma unroll
+    for (int jj = 0; jj < 2; ++jj)
+      *reinterpret_cast<f32x4*>(stage + (16 * t + li) * WIDE_STAGE_ROW + (8 * g + 4 * jj) * 4) = v[t][jj];
+  const int rr = lane >> 3, cc = lane & 7;
+  f32x4 piece[2 * RT];
+#pragma unroll
+  for (int it = 0; it < 2 * RT; ++it)
+    piece[it] = *reinterpret_cast<const f32x4*>(stage + (8 * it + rr) * WIDE_STAGE_ROW + 16 * cc);
+#pragma unroll
+  for (int it = 0; it < 2 * RT; ++it) store16<float>(rs, base + 8 * it + rr, ld, col0 + 4 * cc, piece[it]);
+}
+
+template <typename T, int NT, int RT, bool SLAB>
+__global__ void __launch_bounds__(256) block_tail_sliced_kernel(TailArgs a, float* __restrict__ ws) {
+  static_assert(std::is_same<T, __bf16>::value, "the fp32 partials rely on the bf16 accumulator layout");
+  typedef Frag<T> F;
+  typedef typename F::type FR;
+  typedef typename Vec4<T>::type V4;
+  typedef Wide<T> W;
+  constexpr int C = 16 * NT, KC = F::KC, NKC = C / KC, HSL = W::HSL, NH = W::NH;
+  constexpr int NP = C / W::PK;
+  constexpr int UB = 128 * C;
+  constexpr int DPU = C / 32;
+  constexpr int NPU = C / HSL;
+  constexpr int NBUF = 3, AH = NBUF - 1;
+  extern __shared__ __attribute__((aligned(16))) char wide_smem[];
+  char* ring = wide_smem;
+  float* sVec = reinterpret_cast<float*>(wide_smem + NBUF * UB);   // bproj, g2, b2, bias2 [C each], bias1 [the group's slices]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int li = lane & 15, g = lane >> 4;
+  const int nsg = a.hidden / HSL / (int)gridDim.y;   // hidden slices of this group
+  const int s0 = (int)blockIdx.y * nsg;
+  const int nu = NPU + 2 * nsg;                      // units this workgroup walks (>= NPU + 2 > AH): the waits count these
+  char* stage = reinterpret_cast<char*>(sVec + 4 * C + nsg * HSL) + wave * wide_stage_bytes<RT>();
+  const T* attn = reinterpret_cast<const T*>(a.attn);
+  const T* f1 = reinterpret_cast<const T*>(a.f1);
+  const T* wp = reinterpret_cast<const T*>(a.wproj);
+  const T* w1 = reinterpret_cast<const T*>(a.w1);
+  const T* w2 = reinterpret_cast<const T*>(a.w2);
+
+  // unit u: u < NPU: rows u HSL.. of wproj; then, per hidden slice s of the group, rows s HSL.. of w1, columns s HSL.. of w2
+  auto issue_rows = [&](int u, const T* src) {
+    char* buf = ring + (u % NBUF) * UB;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) dma_panel<T, HSL, true>(buf + p * HSL * 128, src + p * W::PK, C, wave, lane);
+  };
+  auto issue_any = [&](int u) {
+    const int s = s0 + ((u - NPU) >> 1);
+    if (u < NPU) issue_rows(u, wp + (int64_t)u * HSL * C);
+    else if (((u - NPU) & 1) == 0) issue_rows(u, w1 + (int64_t)s * HSL * C);
+    else dma_panel<T, C, true>(ring + (u % NBUF) * UB, w2 + (int64_t)s * HSL, a.hidden, wave, lane);
+  };
+  dma_floats(sVec, a.bproj, C, wave, lane);
+  dma_floats(sVec + C, a.g2, C, wave, lane);
+  dma_floats(sVec + 2 * C, a.b2, C, wave, lane);
+  dma_floats(sVec + 3 * C, a.bias2, C, wave, lane);
+  dma_floats(sVec + 4 * C, a.bias1 + s0 * HSL, nsg * HSL, wave, lane);
+#pragma unroll
+  for (int i = 0; i < AH; ++i) issue_any(i);
+  const float *vbp = sVec, *vg2 = sVec + C, *vb2 = sVec + 2 * C, *vbias2 = sVec + 3 * C, *vbias1 = sVec + 4 * C;
+
+  const int64_t base = ((int64_t)blockIdx.x * 4 + wave) * (16 * RT);
+  int64_t rc[RT];
+#pragma unroll
+  for (int t = 0; t < RT; ++t) {
+    const int64_t row = base + 16 * t + li;
+    rc[t] = row < a.m ? row : a.m - 1;
+  }
+  // ---- f2 = attn @ Wproj^T + b + f1
+  FR xa[RT][NKC];
+#pragma unroll
+  for (int t = 0; t < RT; ++t)
+#pragma unroll
+    for (int kc = 0; kc < NKC; ++kc) xa[t][kc] = *reinterpret_cast<const FR*>(attn + rc[t] * C + KC * kc + F::E * g);
+  f32x4 f2[RT][NT];
+#pragma unroll
+  for (int t = 0; t < RT; ++t)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) f2[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  int u = 0;
+#pragma unroll
+  for (int pt = 0; pt < NPU; ++pt, ++u) {
+    wide_sync<DPU, AH, 0>(u, nu);
+    if (u + AH < nu) issue_any(u + AH);
+    unit_gemm<T, RT, NH, NKC, true>(ring + (u % NBUF) * UB, HSL, xa, f2, pt * NH, li, g);
+  }
+  // ---- + bias + f1, LayerNorm_2 -> B fragments of fc1; f2 stays (rounded to T, packed) as the MLP's residual
+  FR xf[RT][NKC];
+  V4 f2p[RT][NT];
+#pragma unroll
+  for (int t = 0; t < RT; ++t) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const int ch = ChMap<T>::ch(j, g);
+      const f32x4 b = *reinterpret_cast<const f32x4*>(vbp + ch);
+      float s[4];
+      unpack4<T>(*reinterpret_cast<const V4*>(f1 + rc[t] * C + ch), s);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) f2[t][j][r] = round_to<T>(f2[t][j][r] + b[r] + s[r]);
+      f2p[t][j] = pack4<T>(f2[t][j][0], f2[t][j][1], f2[t][j][2], f2[t][j][3]);
+    }
+    float mean, rstd;
+    row_norm<NT>(f2[t], a.eps, mean, rstd);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const int ch = ChMap<T>::ch(j, g);
+      const f32x4 gm = *reinterpret_cast<const f32x4*>(vg2 + ch), bt = *reinterpret_cast<const f32x4*>(vb2 + ch);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) f2[t][j][r] = round_to<T>((f2[t][j][r] - mean) * rstd * gm[r] + bt[r]);
+    }
+#pragma unroll
+    for (int kc = 0; kc < NKC; ++kc) xf[t][kc] = ChainFrag<T, NT>::get(f2[t], kc);
+  }
+  // ---- the group's share of fc2(GELU(fc1(t5)))
+  f32x4 o[RT][NT];
+#pragma unroll
+  for (int t = 0; t < RT; ++t)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) o[t][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < nsg; ++s) {
+    wide_sync<DPU, AH, 0>(u, nu);
+    if (u + AH < nu) issue_any(u + AH);
+    const char* buf = ring + (u % NBUF) * UB;
+    ++u;
+    f32x4 h[RT][NH];
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+      for (int jj = 0; jj < NH; ++jj) h[t][jj] = f32x4{0.f, 0.f, 0.f, 0.f};
+    unit_gemm<T, RT, NH, NKC, true>(buf, HSL, xf, h, 0, li, g);
+#pragma unroll
+    for (int jj = 0; jj < NH; ++jj) {
+      const f32x4 b = *reinterpret_cast<const f32x4*>(vbias1 + s * HSL + ChMap<T>::ch(jj, g));
+#pragma unroll
+      for (int t = 0; t < RT; ++t) gelu_bias4<T>(h[t][jj], b);
+    }
+    FR hf[RT][2];
+#pragma unroll
+    for (int t = 0; t < RT; ++t)
+#pragma unroll
+      for (int mm = 0; mm < 2; ++mm) hf[t][mm] = ChainFrag<T, NH>::get(h[t], mm);
+    wide_sync<DPU, AH, 0>(u, nu);
+    if (u + AH < nu) issue_any(u + AH);
+    buf = ring + (u % NBUF) * UB;
+    ++u;
+    unit_gemm<T, RT, NT, 2, false>(buf, C, hf, o, 0, li, g);
+  }
+  if constexpr (!SLAB) {
+    // ---- + bias2 + f2, out in pieces of HSL channels
+    const __amdgpu_buffer_rsrc_t ors = out_rsrc<T>(reinterpret_cast<T*>(a.out), a.m, C);
+#pragma unroll
+    for (int jg = 0; jg < NT / NH; ++jg) {
+      f32x4 v[RT][NH];
+#pragma unroll
+      for (int t = 0; t < RT; ++t)
+#pragma unroll
+        for (int jj = 0; jj < NH; ++jj) {
+          const int j = jg * NH + jj;
+          const f32x4 b = *reinterpret_cast<const f32x4*>(vbias2 + ChMap<T>::ch(j, g));
+          float r2[4];
+          unpack4<T>(f2p[t][j], r2);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[t][jj][r] = o[t][j][r] + b[r] + r2[r];
+        }
+      wave_store_tile<T, RT, NH, true>(stage, v, ors, C, jg * HSL, base, li, g, lane);
+    }
+  } else {
+    // ---- the fp32 partial, 32 channels (two tiles) at a time; group 0 carries bias2 + f2
+    const __amdgpu_buffer_rsrc_t srs = out_rsrc<float>(ws + (int64_t)blockIdx.y * a.m * C, a.m, C);
+    const bool first = blockIdx.y == 0;
+#pragma unroll
+    for (int q = 0; q < NT / 2; ++q) {
+      f32x4 v[RT][2];
+#pragma unroll
+      for (int t = 0; t < RT; ++t)
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) {
+          const int j = 2 * q + jj;
+          v[t][jj] = o[t][j];
+          if (first) {
+            const f32x4 b = *reinterpret_cast<const f32x4*>(vbias2 + ChMap<T>::ch(j, g));
+            float r2[4];
+            unpack4<T>(f2p[t][j], r2);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[t][jj][r] = o[t][j][r] + b[r] + r2[r];
+          }
+        }
+      wave_store_slab<RT>(stage, v, srs, C, 32 * q, base, li, g, lane);
+    }
+  }
+}
+
+// out = bf16(slab 0 + slab 1 + ... in that order): one thread per 8 channels of a row, every slab's loads of a batch
+// in flight together (slab_sum, common.h)
+template <int B>
+__global__ void __launch_bounds__(256) tail_sliced_finish_kernel(const float* __restrict__ ws, int groups, int64_t n8,
+                                                                 int64_t stride_bytes, __bf16* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n8) return;
+  f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+  const int off[2] = {(int)(t * 32), (int)(t * 32 + 16)};
+  slab_sum<2, B>(acc, slab_rsrc(ws, stride_bytes, groups), off, (int)stride_bytes, groups);
+  const float v[8] = {acc[0][0], acc[0][1], acc[0][2], acc[0][3], acc[1][0], acc[1][1], acc[1][2], acc[1][3]};
+  *reinterpret_cast<s16x8*>(out + t * 8) = FragF<__bf16>::pack(v);
+}
+
+// ------------------------------------------------------------------------------------------------------------
 template <typename T, int NT, int RT, int NBUF, int WGS = 1>
 __global__ void __launch_bounds__(256, WGS) block_head_wide_kernel(HeadArgs a) {
   typedef Frag<T> F;
@@ -818,6 +1039,74 @@ void launch_block_tail_wide(const TailArgs& a0, int c, int dtype, hipStream_t s)
   }
 }
 
+// ---- ptv3_block_tail_sliced: capability, policy and launch
+constexpr int SLICED_MAX_GROUPS = 16;
+static bool sliced_capable(int c, int hidden, int dtype, int64_t m) {
+  return dtype == PTV3_BF16 && (c == 128 || c == 256) && hidden == 4 * c && m >= 1 &&
+         m * c * (int64_t)sizeof(float) < ((int64_t)1 << 31) - (1 << 20);   // a slab's rows through 32-bit byte offsets
+}
+static bool sliced_groups_ok(int hidden, int groups) {
+  return groups >= 1 && groups <= SLICED_MAX_GROUPS && (hidden / 64) % groups == 0;
+}
+template <int RT> static size_t sliced_lds(int c, int hidden, int groups) {
+  return (size_t)3 * 128 * c + (size_t)(4 * c + hidden / groups) * sizeof(float) + 4 * wide_stage_bytes<RT>();
+}
+// One 16-row tile per wave, 64 rows per workgroup: at 1 388 rows 20.4 us with 8 groups against 25.0 us for the best
+// grid of 128-row workgroups (16 groups), the finish launch included (profiles/tail_sliced/README.md).
+constexpr int SLICED_RT = 1;
+// Groups for m rows: as many as keep row tiles x groups within one round of the 256 CUs, and at most 8: with 16 a group
+// is the four proj units and ONE slice pair, and the redundant proj share outweighs the shorter walk (512 rows: 18.0
+// against 17.0 us)
+// C = 128: one group at every measured row count (1 359 ... 16 384: a unit is 16 KB and a quarter of the matrix-core
+// work, the whole walk of 18 units takes 14 us, and any split pays a finish launch on top) - the streaming tail with
+// 64-row workgroups, no partials.
+static int sliced_groups(int c, int hidden, int64_t m) {
+  if (const char* e = getenv("PTV3_TAIL_SLICED_GROUPS")) {
+    const int v = atoi(e);
+    if (sliced_groups_ok(hidden, v)) return v;
+  }
+  if (c == 128) return 1;
+  const int64_t tiles = cdiv(m, 64 * SLICED_RT);
+  int g = 8;
+  while (g > 1 && (tiles * g > 256 || !sliced_groups_ok(hidden, g))) g >>= 1;
+  return g;
+}
+// Rows between which the policy takes the sliced tail.  C = 256: measured ahead of the four launches it replaces at
+// 245, 512, 1 388, 2 800 and 4 096 rows (by 17 to 11 us).  C = 128: ahead of block_tail_coop_kernel at 5 590, 11 000
+// and 16 384 rows (14.0 against 21.2, 14.5 against 30.9, 15.1 against 40.9 us), behind it at 2 800 and 1 359 (13.7
+// against 12.5 us).  Not measured outside.
+static bool sliced_rows(int c, int64_t m) {
+  return c == 256 ? (m >= 245 && m <= 4096) : (m >= 5590 && m <= 16384);
+}
+// PTV3_TAIL_SLICED: 0 off, 1 the measured policy (default), 2 every shape the kernel can run (tests, tools)
+static int sliced_policy(int c, int hidden, int dtype, int64_t m) {
+  const char* env = getenv("PTV3_TAIL_SLICED");
+  const int mode = env ? atoi(env) : 1;
+  if (mode == 0 || !sliced_capable(c, hidden, dtype, m) || m >= wide_min_rows(c)) return 0;   // from there block_tail's
+  if (mode != 2 && !sliced_rows(c, m)) return 0;
+  return sliced_groups(c, hidden, m);
+}
+
+template <int NT, int RT>
+static void launch_tail_sliced(const TailArgs& a, int groups, float* ws, hipStream_t s) {
+  constexpr int C = 16 * NT;
+  const dim3 grid((unsigned)cdiv(a.m, 64 * RT), (unsigned)groups);
+  const size_t lds = sliced_lds<RT>(C, a.hidden, groups);
+  if (groups == 1) {
+    ensure_dynamic_lds(reinterpret_cast<const void*>(&block_tail_sliced_kernel<__bf16, NT, RT, false>), 160 * 1024);
+    hipLaunchKernelGGL((block_tail_sliced_kernel<__bf16, NT, RT, false>), grid, dim3(256), lds, s, a, ws);
+    return;
+  }
+  ensure_dynamic_lds(reinterpret_cast<const void*>(&block_tail_sliced_kernel<__bf16, NT, RT, true>), 160 * 1024);
+  hipLaunchKernelGGL((block_tail_sliced_kernel<__bf16, NT, RT, true>), grid, dim3(256), lds, s, a, ws);
+  const int64_t n8 = a.m * C / 8, stride = a.m * C * (int64_t)sizeof(float);
+  const dim3 fgrid((unsigned)cdiv(n8, 256));
+  __bf16* out = reinterpret_cast<__bf16*>(a.out);
+  if (groups == 2) hipLaunchKernelGGL(tail_sliced_finish_kernel<2>, fgrid, dim3(256), 0, s, ws, groups, n8, stride, out);
+  else if (groups == 4) hipLaunchKernelGGL(tail_sliced_finish_kernel<4>, fgrid, dim3(256), 0, s, ws, groups, n8, stride, out);
+  else hipLaunchKernelGGL(tail_sliced_finish_kernel<8>, fgrid, dim3(256), 0, s, ws, groups, n8, stride, out);
+}
+
 // ---- ptv3_rows_linear: capability and launch
 static int rows_hslr(int c, int dtype) {
   const int esz = dtype == PTV3_F32 ? 4 : 2;
@@ -867,6 +1156,51 @@ void launch_rows_linear(const RowsLinArgs& a, int c, int pro, int dtype, hipStre
 }  // namespace ptv3
 
 using namespace ptv3;
+
+extern "C" int ptv3_block_tail_sliced_policy(int c, int hidden, int dtype, int64_t m) {
+  return sliced_policy(c, hidden, dtype, m);
+}
+
+extern "C" size_t ptv3_block_tail_sliced_workspace_bytes(int64_t m, int c, int groups) {
+  if (groups == 0) groups = sliced_policy(c, 4 * c, PTV3_BF16, m);
+  return groups > 1 && m > 0 ? (size_t)groups * m * c * sizeof(float) : 0;
+}
+
+extern "C" int ptv3_block_tail_sliced(const void* attn, const void* f1, const void* wproj, const float* bproj,
+                                      const float* g2, const float* b2, const void* w1, const float* bias1,
+                                      const void* w2, const float* bias2, void* out, int64_t m, int c, int hidden,
+                                      float eps, int dtype, int groups, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  PTV3_REQUIRE(dtype == PTV3_BF16, "block_tail_sliced: bf16 only (dtype %d)", dtype);
+  PTV3_REQUIRE((c == 128 || c == 256) && hidden == 4 * c, "block_tail_sliced: c=%d / hidden=%d not served (c = 128 | 256, hidden = 4 c)", c, hidden);
+  PTV3_REQUIRE(m == 0 || sliced_capable(c, hidden, dtype, m), "block_tail_sliced: m=%lld out of range", (long long)m);
+  if (groups == 0) {
+    groups = sliced_policy(c, hidden, dtype, m);
+    PTV3_REQUIRE(groups != 0 || m == 0, "block_tail_sliced: the policy does not serve m=%lld; name the groups", (long long)m);
+  } else {
+    PTV3_REQUIRE(sliced_groups_ok(hidden, groups), "block_tail_sliced: groups=%d must divide hidden / 64 = %d and be at most %d",
+                 groups, hidden / 64, SLICED_MAX_GROUPS);
+  }
+  if (m == 0) return PTV3_OK;
+  PTV3_REQUIRE(attn && f1 && wproj && bproj && g2 && b2 && w1 && bias1 && w2 && bias2 && out,
+               "block_tail_sliced: every tensor is required");
+  const size_t need = groups > 1 ? (size_t)groups * m * c * sizeof(float) : 0;
+  PTV3_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0),
+               "block_tail_sliced: workspace of %zu bytes, %zu needed for %d groups (16-byte aligned)", workspace_bytes, need, groups);
+  PTV3_REQUIRE((int64_t)need < SLAB_MAX_BYTES, "block_tail_sliced: %zu bytes of partials exceed 32-bit offsets", need);
+  hipStream_t s = (hipStream_t)stream;
+  const TailArgs a{attn, f1, wproj, bproj, g2, b2, w1, bias1, w2, bias2, out, m, hidden, eps};
+  const int prof = prof_begin(s, PROF_LINEAR, 2.0 * m * c * ((double)groups * c + 2.0 * hidden),
+                              ((double)m * c * (2 * groups + 1) + (double)groups * c * c + 2.0 * c * hidden) * 2 +
+                                  (groups > 1 ? 2.0 * need : 0.0),
+                              nullptr, 0, 0.0);
+  prof_kernel(prof, PK_BLOCK_TAIL_SLICED);
+  if (c == 128) launch_tail_sliced<8, SLICED_RT>(a, groups, (float*)workspace, s);
+  else launch_tail_sliced<16, SLICED_RT>(a, groups, (float*)workspace, s);
+  prof_end(prof, s);
+  PTV3_LAUNCH_CHECK();
+  return PTV3_OK;
+}
 
 extern "C" int ptv3_rows_linear_capable(int c, int cout, int dtype, int64_t m) {
   return rows_linear_capable(c, cout, dtype, m) ? 1 : 0;

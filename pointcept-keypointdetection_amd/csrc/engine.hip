@@ -453,12 +453,29 @@ struct Run {
                             d->ln_eps, d->dtype, sf));
       }
       attention(L, P, qkv, t4, C, H, oi, scale);
-      RUN(ptv3_block_tail(t4, f1, proj_w, proj_b, n2_g, n2_b, fc1_w, fc1_b, fc2_w, fc2_b, L.feat, L.n, C, hidden,
-                          d->ln_eps, d->dtype, sf));
+      // C = 128 on a level of some thousand rows: the streaming tail with 64-row workgroups (block_wide.hip) where its
+      // policy takes the level from the cooperative tail; both read the weights in natural layout
+      const int tail_groups = ptv3_block_tail_sliced_policy(C, hidden, d->dtype, L.n);
+      if (tail_groups) {
+        const size_t tail_wsb = ptv3_block_tail_sliced_workspace_bytes(L.n, C, tail_groups);
+        void* tail_ws = tail_wsb ? F->alloc(tail_wsb) : nullptr;
+        RUN(ptv3_block_tail_sliced(t4, f1, proj_w, proj_b, n2_g, n2_b, fc1_w, fc1_b, fc2_w, fc2_b, L.feat, L.n, C, hidden,
+                                   d->ln_eps, d->dtype, tail_groups, tail_ws, tail_wsb, sf));
+      } else {
+        RUN(ptv3_block_tail(t4, f1, proj_w, proj_b, n2_g, n2_b, fc1_w, fc1_b, fc2_w, fc2_b, L.feat, L.n, C, hidden,
+                            d->ln_eps, d->dtype, sf));
+      }
     } else {
       void* t2 = F->alloc(row * C); void* f1 = F->alloc(row * C); void* t3 = F->alloc(row * C);
-      void* qkv = F->alloc(row * 3 * C); void* t4 = F->alloc(row * C); void* f2 = F->alloc(row * C);
-      void* t5 = F->alloc(row * C); void* t6 = F->alloc(row * hidden);
+      void* qkv = F->alloc(row * 3 * C); void* t4 = F->alloc(row * C);
+      // the tail as one hidden-sliced launch + the sum of its partials (block_wide.hip) where the policy serves the
+      // level: neither f2, the LayerNorm output nor the hidden layer exist in memory
+      const int tail_groups = ptv3_block_tail_sliced_policy(C, hidden, d->dtype, L.n);
+      const size_t tail_wsb = tail_groups ? ptv3_block_tail_sliced_workspace_bytes(L.n, C, tail_groups) : 0;
+      void* tail_ws = tail_wsb ? F->alloc(tail_wsb) : nullptr;
+      void* f2 = tail_groups ? nullptr : F->alloc(row * C);
+      void* t5 = tail_groups ? nullptr : F->alloc(row * C);
+      void* t6 = tail_groups ? nullptr : F->alloc(row * hidden);
       const int splits = ptv3_gemm_splits(L.n, C, C, 27, d->dtype);
       // whole-row linears with their LayerNorms folded in (ptv3_rows_linear): every row read once, no LayerNorm launch
       const bool rows = rows_path(L.n, C, hidden);
@@ -481,7 +498,10 @@ struct Run {
         gemm(t3, qkv_w, qkv, L.n, C, 3 * C, 1, nullptr, nullptr, qkv_b, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
       }
       attention(L, P, qkv, t4, C, H, oi, scale);
-      if (rows) {
+      if (tail_groups) {
+        RUN(ptv3_block_tail_sliced(t4, f1, proj_w, proj_b, n2_g, n2_b, fc1_w, fc1_b, fc2_w, fc2_b, L.feat, L.n, C, hidden,
+                                   d->ln_eps, d->dtype, tail_groups, tail_ws, tail_wsb, sf));
+      } else if (rows) {
         RUN(ptv3_rows_linear(t4, nullptr, nullptr, nullptr, nullptr, nullptr, proj_w, proj_b, 0, f1, nullptr, f2, L.n, C, C,
                              d->ln_eps, d->dtype, sf));
         RUN(ptv3_rows_linear(f2, nullptr, nullptr, nullptr, n2_g, n2_b, fc1_w, fc1_b, PTV3_ACT_GELU, nullptr, nullptr, t6,
@@ -491,7 +511,8 @@ struct Run {
         RUN(ptv3_layernorm(f2, n2_g, n2_b, nullptr, t5, nullptr, nullptr, nullptr, L.n, C, d->ln_eps, d->dtype, sf));
         gemm(t5, fc1_w, t6, L.n, C, hidden, 1, nullptr, nullptr, fc1_b, nullptr, nullptr, PTV3_ACT_GELU, nullptr, nullptr, nullptr);
       }
-      gemm(t6, fc2_w, L.feat, L.n, hidden, C, 1, nullptr, nullptr, fc2_b, nullptr, nullptr, 0, f2, nullptr, nullptr);
+      if (!tail_groups)
+        gemm(t6, fc2_w, L.feat, L.n, hidden, C, 1, nullptr, nullptr, fc2_b, nullptr, nullptr, 0, f2, nullptr, nullptr);
     }
     L.conv_feat = L.feat;
     F->off = mark;

@@ -77,6 +77,10 @@ SIGNATURES = {
     "ptv3_conv_head_halo": (c_int, [P, P, P, c_int64, c_int, P, P, P, c_size_t, P, P, P, P, P, P, P, P, P, c_float, c_int, P]),
     "ptv3_block_head": (c_int, [P, P, c_int, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, c_float, c_int, P]),
     "ptv3_block_tail": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, c_int, c_float, c_int, P]),
+    "ptv3_block_tail_sliced_policy": (c_int, [c_int, c_int, c_int, c_int64]),
+    "ptv3_block_tail_sliced_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "ptv3_block_tail_sliced": (c_int, [P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int, c_int, c_float, c_int, c_int, P,
+                                       c_size_t, P]),
     "ptv3_rows_linear_ln_capable": (c_int, [c_int, c_int, c_int]),
     "ptv3_rows_linear_ln": (c_int, [P, P, P, P, P, P, c_int64, c_int, c_int, c_float, c_int, c_int, P]),
     "ptv3_subm_conv_ln_capable": (c_int, [c_int, c_int, c_int]),

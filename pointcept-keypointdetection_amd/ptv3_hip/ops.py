@@ -657,6 +657,45 @@ def block_tail(attn, f1, wproj, bproj, g2, b2, w1, bias1, w2, bias2, eps):
     return out
 
 
+def block_tail_sliced_policy(c, hidden, dtype, m):
+    """group count with which the executor takes ptv3_block_tail_sliced for a block of m rows, 0 where it does not
+    (PTV3_TAIL_SLICED, PTV3_TAIL_SLICED_GROUPS)."""
+    return int(lib.ptv3_block_tail_sliced_policy(int(c), int(hidden), _DT[dtype], int(m)))
+
+
+def block_tail_sliced(attn, f1, wproj, bproj, g2, b2, w1, bias1, w2, bias2, eps, groups=0, out=None, workspace=None):
+    """ops.block_tail for few rows at c = 128 or 256 in bf16 (ptv3_block_tail_sliced): the hidden layer cut across `groups`
+    workgroups per row tile, fp32 partials in `workspace`, summed in group order.  Weights in natural layout."""
+    _chk(attn, "attn", (torch.float32, torch.bfloat16), 2)
+    _chk(f1, "f1", attn.dtype, 2)
+    m, c = attn.shape
+    if tuple(f1.shape) != (m, c):
+        raise RuntimeError("block_tail_sliced: attn and f1 must have the same shape")
+    hidden = int(w1.shape[0])
+    if tuple(wproj.shape) != (c, c) or tuple(w1.shape) != (hidden, c) or tuple(w2.shape) != (c, hidden):
+        raise RuntimeError(f"block_tail_sliced: weights must be {c}x{c}, {hidden}x{c} and {c}x{hidden}")
+    for t, n in ((bproj, c), (g2, c), (b2, c), (bias1, hidden), (bias2, c)):
+        _chk(t, "block_tail_sliced: per-channel vector", torch.float32, 1)
+        if t is None or t.numel() != n:
+            raise RuntimeError("block_tail_sliced: per-channel vector missing or of the wrong length")
+    for t in (wproj, w1, w2):
+        _chk(t, "block_tail_sliced: weight", attn.dtype, 2)
+    if out is None:
+        out = torch.empty_like(attn)
+    _chk(out, "out", attn.dtype, 2)
+    if tuple(out.shape) != (m, c):
+        raise RuntimeError("block_tail_sliced: out shape mismatch")
+    if workspace is None:
+        g = int(groups) or block_tail_sliced_policy(c, hidden, attn.dtype, m)
+        nbytes = lib.ptv3_block_tail_sliced_workspace_bytes(m, c, g) if attn.dtype in _DT else 0
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=attn.device) if nbytes else None
+    lib.check(lib.ptv3_block_tail_sliced(_p(attn), _p(f1), _p(wproj), _p(bproj), _p(g2), _p(b2), _p(w1), _p(bias1),
+                                         _p(w2), _p(bias2), _p(out), m, c, hidden, float(eps), _dt(attn), int(groups),
+                                         _p(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(),
+                                         _stream()), "ptv3_block_tail_sliced")
+    return out
+
+
 def mlp2_fusable(cin, hidden, cout, dtype):
     return bool(lib.ptv3_mlp2_fusable(int(cin), int(hidden), int(cout), _DT[dtype]))
 

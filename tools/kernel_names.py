@@ -29,7 +29,7 @@ def label(name):
         return "gemm_kernel<bf16,32ch>"
     if "gemm_tn_group_kernel" in n:
         return "gemm_tn_group_kernel"
-    m = re.search(r"(rows_linear|block_head_wide|block_tail_wide|block_head_coop|block_tail_coop|block_head|block_tail|mlp2|layernorm|splitk_reduce|pool_feat|"
+    m = re.search(r"(rows_linear|block_head_wide|block_tail_wide|block_tail_sliced|tail_sliced_finish|block_head_coop|block_tail_coop|block_head|block_tail|mlp2|layernorm|splitk_reduce|pool_feat|"
                   r"gemm_tn|attn_bwd_dq|attn_bwd_dkv)_kernel", n)
     if m:
         return m.group(1) + "_kernel"
