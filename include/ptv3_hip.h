@@ -692,6 +692,56 @@ int ptv3_scene_mean_head(const void* feat, const int64_t* offset, int64_t n, int
 int ptv3_scene_mean_bwd(const float* dg, const int64_t* offset, int64_t n, int c, int b, void* dfeat, int dtype,
                         void* stream);
 
+/* ---- classifier / regressor head (DefaultClassifier, PigBodyRegressor; csrc/cls_head.hip) ---------------------
+ * The part of pointcept/models/default.py:289-338 after the backbone: torch_scatter.segment_csr(feat, offset, "mean")
+ * (:322-326), cls_head = Linear(c, h1) -> BatchNorm1d -> ReLU -> Dropout -> Linear(h1, h2) -> BatchNorm1d -> ReLU ->
+ * Dropout -> Linear(h2, out) (:303-313, :330), and - when `target` (b * out) is given - RegressionL1Loss
+ * (pointcept/models/losses/weight_regression_loss.py:30-38) with the column errors PigBodyRegressor logs
+ * (pointcept/models/pig_regressor.py:36-55): stats (1 + out) = { loss_weight * mean |logit - target|,
+ * metric_scale * mean over rows |logit - target| per column }.  Everything is fp32; no atomics, sums in a fixed order
+ * (two runs are bitwise equal).  Rows are walked in tiles of PTV3_CLS_HEAD_ROW_TILE inside one workgroup, any b.
+ * Limits: c a multiple of 8 in [8, 1024]; h1, h2, out each in [1, 512] (ptv3_cls_head_capable answers without an
+ * error); outside them PTV3_ERR_UNSUPPORTED with ptv3_last_error set, before any launch.
+ * ptv3_cls_head_eval: feat (n, c) fp32 / bf16 -> logits (b, out).  Two launches: the pooling partials of
+ *   ptv3_scene_mean, then one workgroup that sums every scene's slabs in ptv3_scene_mean's order (an empty scene gives
+ *   a zero row) and runs the head with the BatchNorms folded into (s, t) and Dropout the identity.  Weights TRANSPOSED:
+ *   w1t (c, h1), w2t (h1, h2), w3t (h2, out).  workspace: ptv3_scene_mean_workspace_bytes(n, c, b).
+ * ptv3_cls_head_train_fwd: g (b, c) pooled rows -> logits (+ stats), one launch, b >= 2.  nn.Linear's own (out, in)
+ *   weights.  BatchNorm with batch statistics (two-pass variance); running_mean / running_var are updated in place
+ *   (momentum, unbiased variance; num_batches_tracked is the caller's).  mask1 (b, h1), mask2 (b, h2): the Dropout
+ *   keep-masks (0 / 1), applied as mask * inv_keep.  save: ptv3_cls_head_save_floats(b, h1, h2, out) floats, the tape.
+ * ptv3_cls_head_train_bwd: two launches.  dlogits (b, out) given, or formed as dloss[0] * loss_weight *
+ *   sign(logit - target) / (b * out) with sign(0) = 0 from the tape (dloss: a DEVICE scalar); exactly one of the two.
+ *   The dloss form needs the tape of a forward that was given `target`: a forward without one tapes zero signs, and
+ *   every gradient then comes out as zero.
+ *   Writes dg (b, c) and the ten parameter gradients; dz: scratch of b * (h1 + h2 + out) floats. */
+#define PTV3_CLS_HEAD_ROW_TILE 8
+typedef struct ptv3_cls_head_params {
+  const float *w1, *b1, *bn1_weight, *bn1_bias;
+  float *bn1_running_mean, *bn1_running_var;
+  const float *w2, *b2, *bn2_weight, *bn2_bias;
+  float *bn2_running_mean, *bn2_running_var;
+  const float *w3, *b3;
+  float bn1_momentum, bn1_eps, bn2_momentum, bn2_eps;
+} ptv3_cls_head_params;
+typedef struct ptv3_cls_head_grads {
+  float *dw1, *db1, *dbn1_weight, *dbn1_bias, *dw2, *db2, *dbn2_weight, *dbn2_bias, *dw3, *db3;
+} ptv3_cls_head_grads;
+int ptv3_cls_head_capable(int c, int h1, int h2, int out);
+int ptv3_cls_head_eval(const void* feat, const int64_t* offset, int64_t n, int c, int b, int dtype, const float* w1t,
+                       const float* b1, const float* s1, const float* t1, int h1, const float* w2t, const float* b2,
+                       const float* s2, const float* t2, int h2, const float* w3t, const float* b3, int out,
+                       const float* target, float loss_weight, float metric_scale, float* logits, float* stats,
+                       void* workspace, size_t workspace_bytes, void* stream);
+size_t ptv3_cls_head_save_floats(int b, int h1, int h2, int out);
+int ptv3_cls_head_train_fwd(const float* g, int b, int c, int h1, int h2, int out, const ptv3_cls_head_params* params,
+                            const float* mask1, const float* mask2, float inv_keep, const float* target,
+                            float loss_weight, float metric_scale, float* save, float* logits, float* stats,
+                            void* stream);
+int ptv3_cls_head_train_bwd(const float* g, int b, int c, int h1, int h2, int out, const ptv3_cls_head_params* params,
+                            const float* dlogits, const float* dloss, float loss_weight, float inv_keep, float* save,
+                            float* dz, float* dg, const ptv3_cls_head_grads* grads, void* stream);
+
 /* ---- voting keypoint head (KeypointSwin3DVote) ---------------------------------------------------------------
  * ptv3_scene_median: out (b, c) fp32, out[s, j] = the LOWER median over the rows i of scene s of x[i, j]
  *   (+ coord[i, j % 3] when coord (n, 3) is given: one fp32 add inside the kernel, so the (n, K, 3) predicted positions

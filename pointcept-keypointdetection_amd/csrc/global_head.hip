@@ -212,7 +212,7 @@ __global__ void __launch_bounds__(SM_THREADS) scene_mean_bwd_kernel(const float*
   }
 }
 
-static int64_t scene_rows_per_chunk(int64_t n) {
+int64_t scene_rows_per_chunk(int64_t n) {
   // ~1024 chunks at any size (4 partial workgroups per CU); at least 64 rows so a chunk is worth a workgroup
   int64_t r = cdiv(cdiv(n, 1024), 16) * 16;
   return r < 64 ? 64 : r;
@@ -234,8 +234,8 @@ static int scene_mean_check(const char* who, const void* feat, const int64_t* of
   return PTV3_OK;
 }
 
-static void scene_mean_partial(const void* feat, const int64_t* offset, int64_t n, int c, int b, int dtype, float* slab,
-                               hipStream_t s) {
+void scene_mean_partial(const void* feat, const int64_t* offset, int64_t n, int c, int b, int dtype, float* slab,
+                        hipStream_t s) {
   const int64_t rb = scene_rows_per_chunk(n);
   const dim3 grid((unsigned)scene_chunks(n, b));
   if (dtype == PTV3_F32)

@@ -48,4 +48,11 @@ __device__ __forceinline__ void chunk_rows(int64_t j, int b, int64_t s, int64_t 
   *r1 = hi > e ? e : hi;
 }
 
+// The pooling partials (global_head.hip), shared with the classifier head (cls_head.hip): rows per chunk for n rows,
+// and the launch of scene_mean_partial_kernel - one fp32 slab row (c floats) per chunk id into `slab`, which holds
+// ptv3_scene_mean_workspace_bytes(n, c, b).  The caller has checked the arguments (scene_mean_check's conditions).
+int64_t scene_rows_per_chunk(int64_t n);
+void scene_mean_partial(const void* feat, const int64_t* offset, int64_t n, int c, int b, int dtype, float* slab,
+                        hipStream_t s);
+
 }  // namespace ptv3

@@ -4,7 +4,7 @@ The reference's pointcept/models/__init__.py:1-45 imports every backbone (spconv
 ocnn, torch_cluster, peft ...) and cannot be imported on a ROCm box; this package replaces it.
 """
 from .builder import MODELS, MODULES, build_model  # noqa: F401
-from .default import DefaultSegmentor, DefaultSegmentorV2  # noqa: F401
+from .default import DefaultSegmentor, DefaultSegmentorV2, DefaultClassifier  # noqa: F401
 from .modules import PointModule, PointSequential, PointModel  # noqa: F401
 from .point_transformer_v3 import *  # noqa: F401,F403
 from .offset_keypoint_ptv3 import OffsetKeypointPTv3  # noqa: F401
@@ -26,3 +26,4 @@ from .keypoint_stratified_transformer import KeypointStratifiedTransformer  # no
 from .octformer import OctFormer  # noqa: F401
 from .keypoint_octformer import KeypointOctFormer  # noqa: F401
 from .offset_keypoint_octformer import OffsetKeypointOctFormer  # noqa: F401
+from .pig_regressor import PigBodyRegressor  # noqa: F401

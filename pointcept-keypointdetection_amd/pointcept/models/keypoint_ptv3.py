@@ -30,10 +30,11 @@ def make_reg_head(in_channels, hidden_dim, num_keypoints):
     )
 
 
-def check_scene_count(model, offset):
+def check_scene_count(model, offset, bn=None):
     """nn.BatchNorm1d refuses one row per channel in training (the reference fails there with one scene per batch);
-    B = len(offset) is a host-side shape, so this needs no synchronisation."""
-    bn = model.reg_head[1]
+    B = len(offset) is a host-side shape, so this needs no synchronisation.  bn: the first BatchNorm behind the pooling
+    (default: reg_head[1]; DefaultClassifier hands in cls_head[1])."""
+    bn = model.reg_head[1] if bn is None else bn
     if model.training and bn.training and offset.shape[0] == 1:
         raise ValueError("Expected more than 1 value per channel when training, got input size "
                          f"{torch.Size([1, bn.num_features])}")

@@ -397,6 +397,54 @@ def scene_mean(feat, offset):
     return SceneMeanFn.apply(feat, offset)
 
 
+class ClsHeadTrainFn(Function):
+    """cls_head of DefaultClassifier in training mode (pointcept/models/default.py:303-313, :330) on the pooled rows
+    g (B, C) fp32: Linear -> BatchNorm1d (batch statistics, running buffers updated in place) -> ReLU -> keep-mask,
+    twice, then the last Linear - one forward launch, two backward launches (csrc/cls_head.hip).
+    target None: -> (logits, None); the gradient arrives through the logits (any criteria).
+    target given (RegressionL1Loss alone): -> (logits, stats), stats[0] = loss_weight * mean |logits - target| and
+    stats[1:] = metric_scale * the column means; ONLY stats[0] carries a gradient (the logits are marked
+    non-differentiable, the column errors are metrics), and the backward forms dlogits from the saved signs."""
+
+    @staticmethod
+    def forward(ctx, g, w1, b1, g1, be1, w2, b2, g2, be2, w3, b3, bn1, bn2, masks, keep, target, loss_weight,
+                metric_scale):
+        g = g.contiguous()
+        params = (w1.detach(), b1.detach(), g1.detach(), be1.detach(), bn1.running_mean, bn1.running_var,
+                  bn1.momentum, bn1.eps, w2.detach(), b2.detach(), g2.detach(), be2.detach(), bn2.running_mean,
+                  bn2.running_var, bn2.momentum, bn2.eps, w3.detach(), b3.detach())
+        if target is not None:
+            target = target.detach().float().contiguous()
+        logits, stats, save = ops.cls_head_train_fwd(g, params, masks[0], masks[1], keep, target, loss_weight,
+                                                     metric_scale)
+        ctx.save_for_backward(g, save, w1, b1, g1, be1, w2, b2, g2, be2, w3, b3)
+        ctx.keep, ctx.loss_weight, ctx.l1 = keep, loss_weight, target is not None
+        ctx.bn = (bn1.momentum, bn1.eps, bn2.momentum, bn2.eps)
+        if ctx.l1:
+            ctx.mark_non_differentiable(logits)
+        return logits, stats
+
+    @staticmethod
+    def backward(ctx, dlogits, dstats):
+        g, save, w1, b1, g1, be1, w2, b2, g2, be2, w3, b3 = ctx.saved_tensors
+        m1, e1, m2, e2 = ctx.bn
+        params = (w1.detach(), b1.detach(), g1.detach(), be1.detach(), None, None, m1, e1,
+                  w2.detach(), b2.detach(), g2.detach(), be2.detach(), None, None, m2, e2, w3.detach(), b3.detach())
+        if ctx.l1:
+            dg, grads = ops.cls_head_train_bwd(g, params, save, ctx.keep, dloss=dstats.float().contiguous(),
+                                               loss_weight=ctx.loss_weight)
+        else:
+            dg, grads = ops.cls_head_train_bwd(g, params, save, ctx.keep, dlogits=dlogits.float().contiguous())
+        return (dg, *grads, None, None, None, None, None, None, None)
+
+
+def cls_head_train(g, head, masks, keep, target=None, loss_weight=1.0, metric_scale=1.0):
+    """head: the nn.Sequential of DefaultClassifier (module indices 0 .. 8)."""
+    return ClsHeadTrainFn.apply(g, head[0].weight, head[0].bias, head[1].weight, head[1].bias, head[4].weight,
+                                head[4].bias, head[5].weight, head[5].bias, head[8].weight, head[8].bias, head[1],
+                                head[5], masks, keep, target, loss_weight, metric_scale)
+
+
 class VoteLossFn(Function):
     """The vote loss of keypoint_swin3d_plus.py:86-164 on the head's raw votes (N, 3K): forward = the two launches of
     ops.vote_loss -> (loss, curves (1 + K), mask count (1 + K) int32), backward = one launch (the mask is recomputed).

@@ -35,6 +35,44 @@ PIGSEG_CRITERIA = [
 PIGSEG_PTV3_CFG = dict(type="DefaultSegmentorV2", num_classes=2, backbone_out_channels=64,
                        backbone=dict(type="PT-v3m1", **FORK_CFG), criteria=PIGSEG_CRITERIA)
 
+# the fork's body-size-and-weight regression: the `model` dict of configs/my_dataset/ptv3_weight.py:40-77, verbatim (no
+# dec_* keys: the backbone's defaults hold; enc_num_head gives head dimension 32 at every encoder level)
+PIG_WEIGHT_PTV3_CFG = dict(
+    type="PigBodyRegressor",
+    criteria=[dict(type="RegressionL1Loss", loss_weight=1.0)],
+    num_classes=7,
+    backbone_embed_dim=64,
+    backbone=dict(
+        type="PT-v3m1",
+        in_channels=4,
+        order=("z", "z-trans", "hilbert", "hilbert-trans"),
+        stride=(2, 2, 2, 2),
+        enc_depths=(2, 2, 2, 6, 2),
+        enc_channels=(32, 64, 128, 256, 512),
+        enc_num_head=(1, 2, 4, 8, 16),
+        enc_patch_size=(1024, 1024, 1024, 1024, 1024),
+        dec_patch_size=(1024, 1024, 1024, 1024),
+        mlp_ratio=4,
+        qkv_bias=True,
+        qk_scale=None,
+        attn_drop=0.0,
+        proj_drop=0.0,
+        drop_path=0.3,
+        shuffle_orders=True,
+        pre_norm=True,
+        enable_rpe=False,
+        enable_flash=False,
+        upcast_attention=False,
+        upcast_softmax=False,
+        pdnorm_bn=False,
+        pdnorm_ln=False,
+        pdnorm_decouple=True,
+        pdnorm_adaptive=False,
+        pdnorm_affine=True,
+        pdnorm_conditions=("nuisance", 3),
+    ),
+)
+
 # "PT-v3m2" (point_transformer_v3m2_sonata.py) plumbing-size config: GridPooling, LayerScale, LayerNorm stem
 TINY_M2_CFG = dict(
     in_channels=4, order=ORDERS, stride=(2, 2, 2, 2),

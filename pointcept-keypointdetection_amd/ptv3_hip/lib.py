@@ -35,6 +35,20 @@ class BlockTrain(ctypes.Structure):
                 [("workspace_bytes", c_size_t), ("attn_lse", P)])
 
 
+class ClsHeadParams(ctypes.Structure):
+    """struct ptv3_cls_head_params of include/ptv3_hip.h (field for field)"""
+    _fields_ = ([(k, P) for k in ("w1", "b1", "bn1_weight", "bn1_bias", "bn1_running_mean", "bn1_running_var",
+                                  "w2", "b2", "bn2_weight", "bn2_bias", "bn2_running_mean", "bn2_running_var",
+                                  "w3", "b3")] +
+                [(k, c_float) for k in ("bn1_momentum", "bn1_eps", "bn2_momentum", "bn2_eps")])
+
+
+class ClsHeadGrads(ctypes.Structure):
+    """struct ptv3_cls_head_grads of include/ptv3_hip.h (field for field)"""
+    _fields_ = [(k, P) for k in ("dw1", "db1", "dbn1_weight", "dbn1_bias", "dw2", "db2", "dbn2_weight", "dbn2_bias",
+                                 "dw3", "db3")]
+
+
 # name -> (restype, argtypes); must list every symbol include/ptv3_hip.h declares
 SIGNATURES = {
     "ptv3_last_error": (c_char_p, []),
@@ -149,6 +163,14 @@ SIGNATURES = {
     "ptv3_scene_mean_head": (c_int, [P, P, c_int64, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, c_int, P, P,
                                      c_size_t, P]),
     "ptv3_scene_mean_bwd": (c_int, [P, P, c_int64, c_int, c_int, P, c_int, P]),
+    "ptv3_cls_head_capable": (c_int, [c_int, c_int, c_int, c_int]),
+    "ptv3_cls_head_eval": (c_int, [P, P, c_int64, c_int, c_int, c_int, P, P, P, P, c_int, P, P, P, P, c_int, P, P, c_int,
+                                   P, c_float, c_float, P, P, P, c_size_t, P]),
+    "ptv3_cls_head_save_floats": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "ptv3_cls_head_train_fwd": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_float, P, c_float, c_float, P,
+                                        P, P, P]),
+    "ptv3_cls_head_train_bwd": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_float, c_float, P, P, P, P,
+                                        P]),
     "ptv3_scene_median_workspace_bytes": (c_size_t, [c_int, c_int]),
     "ptv3_scene_median": (c_int, [P, P, P, c_int64, c_int, c_int, P, P, c_size_t, P]),
     "ptv3_vote_loss_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),

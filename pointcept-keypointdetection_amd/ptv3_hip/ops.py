@@ -1238,6 +1238,124 @@ def scene_mean_bwd(dg, offset, n, dtype):
 
 
 # ---------------------------------------------------------------------------------------------
+# classifier / regressor head (DefaultClassifier, PigBodyRegressor)
+# ---------------------------------------------------------------------------------------------
+CLS_HEAD_ROW_TILE = 8   # PTV3_CLS_HEAD_ROW_TILE
+
+
+def cls_head_capable(c, h1, h2, out):
+    """True when the batch head kernels take these widths (ptv3_cls_head_capable)."""
+    return bool(lib.ptv3_cls_head_capable(int(c), int(h1), int(h2), int(out)))
+
+
+def _cls_target(target, b, out, dev):
+    if target is None:
+        return None, None
+    _chk(target, "target", torch.float32)
+    if target.numel() != b * out:
+        raise RuntimeError(f"cls_head: target has {target.numel()} elements, expected {b} x {out}")
+    return target, torch.empty(1 + out, dtype=torch.float32, device=dev)
+
+
+def cls_head_eval(feat, offset, w1t, b1, s1, t1, w2t, b2, s2, t2, w3t, b3, target=None, loss_weight=1.0,
+                  metric_scale=1.0):
+    """(logits (B, out) fp32, stats (1 + out) or None): per-scene mean of feat (N, C) fp32 / bf16, then the head with
+    folded BatchNorms in fp32 on TRANSPOSED weights w1t (C, H1), w2t (H1, H2), w3t (H2, out); with `target` (B * out)
+    stats = [loss_weight * mean |logits - target|, metric_scale * column means of |logits - target|].  Two launches
+    (ptv3_cls_head_eval)."""
+    _chk(feat, "feat", _F, 2)
+    off = _scene_offset(offset, "offset")
+    for t, nm in ((w1t, "w1t"), (w2t, "w2t"), (w3t, "w3t")):
+        _chk(t, nm, torch.float32, 2)
+    for t, nm in ((b1, "b1"), (s1, "s1"), (t1, "t1"), (b2, "b2"), (s2, "s2"), (t2, "t2"), (b3, "b3")):
+        _chk(t, nm, torch.float32, 1)
+    n, c = feat.shape
+    h1, h2, o = w1t.shape[1], w2t.shape[1], w3t.shape[1]
+    if w1t.shape[0] != c or w2t.shape[0] != h1 or w3t.shape[0] != h2 or any(t.shape[0] != h1 for t in (b1, s1, t1)) \
+            or any(t.shape[0] != h2 for t in (b2, s2, t2)) or b3.shape[0] != o:
+        raise RuntimeError("cls_head_eval: shape mismatch")
+    b = off.shape[0]
+    target, stats = _cls_target(target, b, o, feat.device)
+    logits = torch.empty((b, o), dtype=torch.float32, device=feat.device)
+    nb = lib.ptv3_scene_mean_workspace_bytes(n, c, b)
+    ws = _ws(nb, feat.device)
+    lib.check(lib.ptv3_cls_head_eval(_p(feat), _p(off), n, c, b, _dt(feat), _p(w1t), _p(b1), _p(s1), _p(t1), h1,
+                                     _p(w2t), _p(b2), _p(s2), _p(t2), h2, _p(w3t), _p(b3), o, _p(target),
+                                     float(loss_weight), float(metric_scale), _p(logits), _p(stats), _p(ws), nb,
+                                     _stream()), "ptv3_cls_head_eval")
+    return logits, stats
+
+
+def _cls_params(w1, b1, g1, be1, rm1, rv1, mom1, eps1, w2, b2, g2, be2, rm2, rv2, mom2, eps2, w3, b3):
+    from .lib import ClsHeadParams
+    for t, nm in ((w1, "w1"), (w2, "w2"), (w3, "w3")):
+        _chk(t, nm, torch.float32, 2)
+    for t, nm in ((b1, "b1"), (g1, "bn1.weight"), (be1, "bn1.bias"), (rm1, "bn1.running_mean"),
+                  (rv1, "bn1.running_var"), (b2, "b2"), (g2, "bn2.weight"), (be2, "bn2.bias"),
+                  (rm2, "bn2.running_mean"), (rv2, "bn2.running_var"), (b3, "b3")):
+        _chk(t, nm, torch.float32, 1)
+    h1, c = w1.shape
+    h2, o = w2.shape[0], w3.shape[0]
+    if w2.shape[1] != h1 or w3.shape[1] != h2 or any(t is not None and t.shape[0] != h1 for t in (b1, g1, be1, rm1, rv1)) \
+            or any(t is not None and t.shape[0] != h2 for t in (b2, g2, be2, rm2, rv2)) or b3.shape[0] != o:
+        raise RuntimeError("cls_head: parameter shape mismatch")
+    p = ClsHeadParams(_p(w1), _p(b1), _p(g1), _p(be1), _p(rm1), _p(rv1), _p(w2), _p(b2), _p(g2), _p(be2), _p(rm2),
+                      _p(rv2), _p(w3), _p(b3), float(mom1), float(eps1), float(mom2), float(eps2))
+    return p, (c, h1, h2, o)
+
+
+def cls_head_train_fwd(g, params, mask1, mask2, keep, target=None, loss_weight=1.0, metric_scale=1.0):
+    """Training forward of the head on the pooled rows g (B, C) fp32, one launch (ptv3_cls_head_train_fwd).
+    params: the 18 arguments of _cls_params (nn.Linear's own weights; both BatchNorms' affine, running buffers - updated
+    in place -, momentum, eps).  mask1 (B, H1) / mask2 (B, H2): 0 / 1 keep-masks, applied as mask / keep.
+    -> (logits (B, out), stats (1 + out) or None, save): `save` is the tape cls_head_train_bwd takes."""
+    _chk(g, "g", torch.float32, 2)
+    p, (c, h1, h2, o) = _cls_params(*params)
+    b = g.shape[0]
+    _chk(mask1, "mask1", torch.float32, 2)
+    _chk(mask2, "mask2", torch.float32, 2)
+    if g.shape[1] != c or tuple(mask1.shape) != (b, h1) or tuple(mask2.shape) != (b, h2):
+        raise RuntimeError("cls_head_train_fwd: shape mismatch")
+    target, stats = _cls_target(target, b, o, g.device)
+    logits = torch.empty((b, o), dtype=torch.float32, device=g.device)
+    save = torch.empty(max(lib.ptv3_cls_head_save_floats(b, h1, h2, o), 1), dtype=torch.float32, device=g.device)
+    lib.check(lib.ptv3_cls_head_train_fwd(_p(g), b, c, h1, h2, o, ctypes.addressof(p), _p(mask1), _p(mask2),
+                                          1.0 / float(keep), _p(target), float(loss_weight), float(metric_scale),
+                                          _p(save), _p(logits), _p(stats), _stream()), "ptv3_cls_head_train_fwd")
+    return logits, stats, save
+
+
+def cls_head_train_bwd(g, params, save, keep, dlogits=None, dloss=None, loss_weight=1.0):
+    """Backward of cls_head_train_fwd, two launches (ptv3_cls_head_train_bwd).  Either dlogits (B, out) or dloss (a
+    device scalar: then dlogits = dloss * loss_weight * sign(logits - target) / (B * out), sign from the tape).
+    -> (dg (B, C), [dW1, db1, dbn1.weight, dbn1.bias, dW2, db2, dbn2.weight, dbn2.bias, dW3, db3])."""
+    from .lib import ClsHeadGrads
+    _chk(g, "g", torch.float32, 2)
+    _chk(save, "save", torch.float32, 1)
+    p, (c, h1, h2, o) = _cls_params(*params)
+    b = g.shape[0]
+    if g.shape[1] != c or save.numel() < lib.ptv3_cls_head_save_floats(b, h1, h2, o):
+        raise RuntimeError("cls_head_train_bwd: shape mismatch")
+    if dlogits is not None:
+        _chk(dlogits, "dlogits", torch.float32, 2)
+        if tuple(dlogits.shape) != (b, o):
+            raise RuntimeError("cls_head_train_bwd: dlogits shape mismatch")
+    if dloss is not None:
+        _chk(dloss, "dloss", torch.float32)
+        if dloss.numel() < 1:
+            raise RuntimeError("cls_head_train_bwd: dloss is empty")
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=g.device)  # noqa: E731
+    grads = [new(h1, c), new(h1), new(h1), new(h1), new(h2, h1), new(h2), new(h2), new(h2), new(o, h2), new(o)]
+    dg = new(b, c)
+    dz = new(b * (h1 + h2 + o))
+    gs = ClsHeadGrads(*[_p(t) for t in grads])
+    lib.check(lib.ptv3_cls_head_train_bwd(_p(g), b, c, h1, h2, o, ctypes.addressof(p), _p(dlogits), _p(dloss),
+                                          float(loss_weight), 1.0 / float(keep), _p(save), _p(dz), _p(dg),
+                                          ctypes.addressof(gs), _stream()), "ptv3_cls_head_train_bwd")
+    return dg, grads
+
+
+# ---------------------------------------------------------------------------------------------
 # voting keypoint head
 # ---------------------------------------------------------------------------------------------
 def scene_median(x, coord, offset):
