@@ -1132,6 +1132,90 @@ int ptv3_focal_bwd(const float* dloss, const float* logits, const int64_t* label
                    const int32_t* nvalid, int64_t n, int C, int64_t ignore_index, float gamma, float loss_weight, int mean,
                    float* dlogits, void* stream);
 
+/* ---- PointGroup (pointcept/models/point_group/point_group_v1m1_base.py, libs/pointgroup_ops; the CUDA library cannot be
+ * built for the fixtures: PARITY WITH pointgroup_ops UNPINNED) ----------------------------------------------------------
+ * All entry points are fp32 / int32.  The ball query and the clustering share one workspace layout,
+ * ptv3_pg_workspace_bytes(n) bytes, 16-byte aligned; n <= 2 000 000 (n * 1000 list entries fit an int32), at most 32767
+ * scenes.  Both lay the points over a grid of edge 1.01 * radius (the 1 % covers the fp32 rounding of a cell position),
+ * sort them by cell with ptv3_argsort_i64 and visit, per point, 9 runs of the sorted order.
+ *
+ * ptv3_pg_ballquery_batch_p: ballquery_batch_p of libs/pointgroup_ops/src/bfs_cluster_kernel.cu:16-91 and the retry
+ *   loop of functions/functions.py:26-35.  The neighbours of point i are the rows k of its own scene with
+ *   d2 = (xi-xk)^2 + (yi-yk)^2 + (zi-zk)^2 < radius^2 (:37-38, one fp32 rounding per operation, i included), in ascending
+ *   k, at most the first 1000 (:21, :39-44).  start_len (n, 2) = (start, count); idx = the lists back to back.  The
+ *   reference hands `start` out by atomicAdd in arrival order (:49); here start is the exclusive scan of count by point
+ *   index - one of the reference's possible outputs, and bitwise repeatable.  batch_idxs (n) may be NULL (the scene is
+ *   then found in batch_offsets); batch_offsets (num_scenes + 1) starts with 0.  Two calls on one workspace:
+ *     idx == NULL: count pass, scan, start_len; *n_active (host) receives the number of list entries (one
+ *                  synchronisation).  No meanActive retry: the count sizes idx exactly.
+ *     idx != NULL: fills idx (*n_active entries) from the state the first call left in the workspace.  One wave per
+ *                  point: up to 1000 hits are gathered from the 9 runs and put in index order in LDS; a point with more
+ *                  scans its scene in index order like the reference and stops at 1000, so it keeps the 1000 lowest.
+ * ptv3_pg_cluster: ballquery_batch_p + bfs_cluster (bfs_cluster.cpp:53-137) without the lists, the copy and the host
+ *   search.  xyz (n, 3) the compacted centres, label (n), offsets (num_scenes + 1) from 0.  Every point counts all its
+ *   neighbours and unions itself with each same-label neighbour of smaller index; a union hooks the larger root under
+ *   the smaller by compare-and-swap (the only atomics), so a component's root is its smallest member whichever thread
+ *   wins.  Components of size >= min_points are written ordered by smallest member, members ascending:
+ *   cluster_idxs (., 2) = (cluster, point), cluster_offsets (clusters + 1); both are sized by the caller for the worst
+ *   case, (n, 2) and (n + 1).  record_host[4] = clusters, list entries, 1 when a point has more than 1000 neighbours,
+ *   clusters with more than propose_points members; it is read back once, the call's only synchronisation.  With the
+ *   flag set the reference's lists would be cut and its graph directed, which a union cannot follow: the call returns
+ *   PTV3_PG_TRUNCATED and the caller takes ptv3_pg_ballquery_batch_p + ptv3_pg_bfs_cluster_host.
+ * ptv3_pg_bfs_cluster_host: find_cc / get_clusters / fill_cluster_idxs_ of bfs_cluster.cpp:53-111 on host arrays, from
+ *   the algorithm: directed lists, seeds in ascending index, members in discovery order.  cluster_idxs (n, 2) and
+ *   cluster_offsets (n + 1) sized for the worst case; counts[2] = clusters, list entries.  Returns 1 on a bad argument,
+ *   2 when a list or an entry points outside the arrays.  Touches no GPU.
+ * ptv3_pg_proposals: point_group_v1m1_base.py:145-174 on the device.  Keeps the clusters with MORE than propose_points
+ *   members (:154; min_points above is >=), num_proposals of them as the caller knows from the record or the offsets.
+ *   pred_classes (P) int64 = segment_pred of the cluster's first member, pred_scores (P) = the mean over the members of
+ *   prob[row, class] (thread t of 256 adds members t, t + 256, ... in order, then a fixed tree: repeatable),
+ *   pred_masks (P, n_rows) int32.  row_map (n_map, optional): cluster_idxs[:, 1] index it and it gives the row (:141-143).
+ *   slot: (num_clusters) int32 scratch.  No atomics, no synchronisation. */
+#define PTV3_PG_TRUNCATED 16
+size_t ptv3_pg_workspace_bytes(int64_t n);
+int ptv3_pg_ballquery_batch_p(const float* xyz, const int32_t* batch_idxs, const int32_t* batch_offsets, int num_scenes,
+                              int64_t n, float radius, int32_t* start_len, int32_t* idx, int64_t* n_active,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int ptv3_pg_cluster(const float* xyz, const int32_t* label, const int32_t* offsets, int num_scenes, int64_t n,
+                    float radius, int min_points, int propose_points, int32_t* cluster_idxs, int32_t* cluster_offsets,
+                    int32_t* record_host, void* workspace, size_t workspace_bytes, void* stream);
+int ptv3_pg_bfs_cluster_host(const int32_t* semantic_label, const int32_t* ball_query_idxs, int64_t n_active,
+                             const int32_t* start_len, int64_t n, int threshold, int32_t* cluster_idxs,
+                             int32_t* cluster_offsets, int32_t* counts);
+int ptv3_pg_proposals(const int32_t* cluster_idxs, const int32_t* cluster_offsets, int num_clusters, int64_t sum,
+                      const float* prob, int num_classes, const int64_t* segment_pred, const int64_t* row_map,
+                      int64_t n_map, int64_t n_rows, int propose_points, int num_proposals, int64_t* pred_classes,
+                      float* pred_scores, int32_t* pred_masks, int32_t* slot, void* stream);
+
+/* ptv3_pg_head_eval: both heads of PointGroup and what eval derives from them (point_group_v1m1_base.py:66-67, :101-117)
+ *   in one launch.  feat (n, C) fp32, C = 64 or 96, 1 .. 256 classes (ptv3_pg_head_eval_capable).  bias_pred (n, 3) =
+ *   Linear(w2, b2)(relu(BatchNorm(Linear(w1, b1)(feat)))) with the running statistics (scale = weight / sqrt(var + eps),
+ *   the reference builds the norm with eps 1e-3); logit (n, K) = Linear(w_seg, b_seg)(feat); prob = softmax(logit);
+ *   segment_pred (n) int64 = the first maximum of logit (the reference takes it of prob, :105: the same index unless two
+ *   probabilities round together); center (n, 3) = (coord + bias_pred) / voxel_size, one rounding per operation as
+ *   torch's add and div (:102-103); keep (n) uint8 = segment_pred is none of ignore_host[0 .. num_ignore) (:107-117,
+ *   at most 8).  Weights are torch's (out, in) row-major.  All weights are staged once per workgroup in LDS (151 KB at
+ *   C = 96 with 256 classes); a workgroup then walks tiles of 8 rows.  fp32 fma chains in input-channel order, no atomics.
+ * ptv3_pg_bias_loss_fwd: :75-89.  mask = instance != ignore_index, g = centroid - coord; out[0] = sum mask |p - g|_1 /
+ *   (sum mask + 1e-8), out[1] = sum mask (-(p / (|p| + 1e-8)) . (g / (|g| + 1e-8))) / (sum mask + 1e-8), out[2] = the
+ *   denominator (kept for the backward).  One launch of one workgroup: thread t of 1024 adds rows t, t + 1024, ... in
+ *   that order in float64, then a fixed tree - a two-stage fixed-order reduction, no atomics, bitwise repeatable.  Both
+ *   losses are 0 when no row is unmasked.
+ * ptv3_pg_bias_loss_bwd: autograd of the two losses with respect to bias_pred (n, 3), one launch; dloss[2] = the
+ *   gradients arriving at out[0] and out[1], on the device.  At p == 0 the gradient of |p| is 0 as torch.norm's is (so
+ *   only the v / (|p| + eps) term is left), and sign(0) = 0 as torch.abs's; masked rows get 0. */
+int ptv3_pg_head_eval_capable(int c, int num_classes);
+int ptv3_pg_head_eval(const float* feat, const float* coord, int64_t n, int c, int num_classes, const float* w1,
+                      const float* b1, const float* bn_weight, const float* bn_bias, const float* bn_mean,
+                      const float* bn_var, float bn_eps, const float* w2, const float* b2, const float* w_seg,
+                      const float* b_seg, float voxel_size, const int* ignore_host, int num_ignore, float* bias_pred,
+                      float* logit, float* prob, int64_t* segment_pred, float* center, uint8_t* keep, void* stream);
+int ptv3_pg_bias_loss_fwd(const float* bias_pred, const float* coord, const float* centroid, const int64_t* instance,
+                          int64_t ignore_index, int64_t n, float* out, void* stream);
+int ptv3_pg_bias_loss_bwd(const float* dloss, const float* bias_pred, const float* coord, const float* centroid,
+                          const int64_t* instance, int64_t ignore_index, int64_t n, const float* fwd_out, float* dbias,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

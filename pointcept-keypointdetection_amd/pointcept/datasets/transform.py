@@ -158,3 +158,40 @@ class GridSample(object):
             self._extras(part, coord, grid, mm, inverse, idx_part)
             parts.append(part)
         return parts
+
+
+@TRANSFORMS.register_module()
+class InstanceParser(object):
+    """transform.py:1239-1282 (CPU numpy; PointGroup's pipelines end in it).  Points of an ignored segment class lose
+    their instance; the remaining instance ids are renumbered 0 .. K-1 in ascending order; every point gets the mean
+    coordinate of its instance (`instance_centroid`, the ignore value elsewhere) and every instance a row of `bbox`:
+    box centre (3), box size (3), angle 0, class - the class index shifted down by the number of non-negative ignored
+    classes below it.  `instance` is rewritten in place, as in the reference."""
+
+    def __init__(self, segment_ignore_index=(-1, 0, 1), instance_ignore_index=-1):
+        self.segment_ignore_index = segment_ignore_index
+        self.instance_ignore_index = instance_ignore_index
+
+    def __call__(self, data_dict):
+        coord, segment, instance = data_dict["coord"], data_dict["segment"], data_dict["instance"]
+        valid = ~np.isin(segment, self.segment_ignore_index)
+        instance[~valid] = self.instance_ignore_index
+        ids, renumbered = np.unique(instance[valid], return_inverse=True)
+        instance[valid] = renumbered
+        vacancy = np.array([c for c in self.segment_ignore_index if c >= 0], dtype=coord.dtype)
+        centroid = np.full((coord.shape[0], 3), self.instance_ignore_index, dtype=np.float64)
+        bbox = np.full((len(ids), 8), self.instance_ignore_index, dtype=np.float64)
+        for k in range(len(ids)):
+            member = instance == k
+            pts = coord[member]
+            lo, hi = pts.min(0), pts.max(0)
+            cls = coord.dtype.type(segment[member][0])
+            centroid[member] = pts.mean(0)
+            bbox[k, 0:3] = (hi + lo) / 2
+            bbox[k, 3:6] = hi - lo
+            bbox[k, 6] = 0
+            bbox[k, 7] = cls - np.greater(cls, vacancy).sum()
+        data_dict["instance"] = instance
+        data_dict["instance_centroid"] = centroid
+        data_dict["bbox"] = bbox
+        return data_dict

@@ -811,3 +811,28 @@ def block(feat, conv_feat, blk_params, nbr, row_order, wo, wi, heads, patch, sca
                                    cu, float(k1), float(k2))
     return BlockFn.apply(feat, conv_feat, *blk_params, nbr, row_order, wo, wi, heads, patch, scale,
                          drop_factor(drop1, feat.dtype), drop_factor(drop2, feat.dtype), eps, cu)
+
+
+class PGBiasLossFn(Function):
+    """PointGroup's masked L1 and negative-cosine bias losses (point_group_v1m1_base.py:75-89): forward = one launch
+    (ops.pg_bias_loss), backward = one launch.  Only bias_pred carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, bias_pred, coord, centroid, instance, ignore_index):
+        bias_pred, coord = bias_pred.float().contiguous(), coord.float().contiguous()
+        centroid, instance = centroid.float().contiguous(), instance.contiguous()
+        out = ops.pg_bias_loss(bias_pred, coord, centroid, instance, ignore_index)
+        ctx.save_for_backward(bias_pred, coord, centroid, instance, out)
+        ctx.ignore_index = ignore_index
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, dl1, dcos):
+        bias_pred, coord, centroid, instance, out = ctx.saved_tensors
+        dloss = torch.stack([dl1, dcos]).float().contiguous()
+        return ops.pg_bias_loss_bwd(dloss, bias_pred, coord, centroid, instance, out, ctx.ignore_index), None, None, None, None
+
+
+def pg_bias_loss(bias_pred, coord, centroid, instance, ignore_index=-1):
+    """-> (bias_l1_loss, bias_cosine_loss), 0-d with grad."""
+    return PGBiasLossFn.apply(bias_pred, coord, centroid, instance, ignore_index)

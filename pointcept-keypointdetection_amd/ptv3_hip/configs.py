@@ -175,3 +175,30 @@ TINY_SWIN3D_CFG = dict(
 # the two constructor variants no shipped config uses: GridDownsample (knn_down=False) and the residual stem
 # (stem_transformer=False) - tests/golden/state_dict_swin3d_tiny_grid_resstem.txt lists the reference class built this way
 TINY_SWIN3D_GRID_RESSTEM_CFG = dict(TINY_SWIN3D_CFG, knn_down=False, stem_transformer=False)
+
+# PointGroup instance segmentation on ScanNet: the `model` dicts of configs/scannet/insseg-pointgroup-v1m2-0-ptv3-base.py
+# :37-90 (PG-v1m2 on the PT-v3m1 of bench.py) and configs/scannet/insseg-pointgroup-v1m1-0-spunet-base.py:37-55
+_PG_SCANNET = dict(semantic_num_classes=20, semantic_ignore_index=-1, segment_ignore_index=(-1, 0, 1),
+                   instance_ignore_index=-1, cluster_thresh=1.5, cluster_closed_points=300, cluster_propose_points=100,
+                   cluster_min_points=50)
+PG_PTV3_SCANNET_CFG = dict(
+    type="PG-v1m2",
+    backbone=dict(
+        type="PT-v3m1", in_channels=6, order=("z", "z-trans", "hilbert", "hilbert-trans"), stride=(2, 2, 2, 2),
+        enc_depths=(2, 2, 2, 6, 2), enc_channels=(32, 64, 128, 256, 512), enc_num_head=(2, 4, 8, 16, 32),
+        enc_patch_size=(1024, 1024, 1024, 1024, 1024), dec_depths=(2, 2, 2, 2), dec_channels=(64, 64, 128, 256),
+        dec_num_head=(4, 4, 8, 16), dec_patch_size=(1024, 1024, 1024, 1024), mlp_ratio=4, qkv_bias=True, qk_scale=None,
+        attn_drop=0.0, proj_drop=0.0, drop_path=0.3, shuffle_orders=True, pre_norm=True, enable_rpe=False,
+        enable_flash=True, upcast_attention=False, upcast_softmax=False, enc_mode=False, pdnorm_bn=False,
+        pdnorm_ln=False, pdnorm_decouple=True, pdnorm_adaptive=False, pdnorm_affine=True,
+        pdnorm_conditions=("ScanNet", "S3DIS", "Structured3D")),
+    backbone_out_channels=64, **_PG_SCANNET,
+    criteria=[dict(type="CrossEntropyLoss", loss_weight=1.0, ignore_index=-1),
+              dict(type="LovaszLoss", mode="multiclass", loss_weight=1.0, ignore_index=-1)],
+)
+PG_SPUNET_SCANNET_CFG = dict(
+    type="PG-v1m1",
+    backbone=dict(type="SpUNet-v1m1", in_channels=6, num_classes=0, channels=(32, 64, 128, 256, 256, 128, 96, 96),
+                  layers=(2, 3, 4, 6, 2, 2, 2, 2)),
+    backbone_out_channels=96, **_PG_SCANNET,
+)

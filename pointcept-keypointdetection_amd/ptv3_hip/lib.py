@@ -4,6 +4,7 @@ import os
 from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_void_p
 
 PTV3_F32, PTV3_BF16 = 0, 1
+PTV3_PG_TRUNCATED = 16  # ptv3_pg_cluster: a point has more than 1000 neighbours (take the list path)
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 ORDER_IDS = {"z": 0, "z-trans": 1, "hilbert": 2, "hilbert-trans": 3}
 
@@ -225,6 +226,16 @@ SIGNATURES = {
     "ptv3_focal_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "ptv3_focal_fwd": (c_int, [P, P, P, c_int64, c_int, c_int64, c_float, c_float, c_int, P, P, P, c_size_t, P]),
     "ptv3_focal_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, c_int64, c_float, c_float, c_int, P, P]),
+    "ptv3_pg_workspace_bytes": (c_size_t, [c_int64]),
+    "ptv3_pg_ballquery_batch_p": (c_int, [P, P, P, c_int, c_int64, c_float, P, P, P, P, c_size_t, P]),
+    "ptv3_pg_cluster": (c_int, [P, P, P, c_int, c_int64, c_float, c_int, c_int, P, P, P, P, c_size_t, P]),
+    "ptv3_pg_bfs_cluster_host": (c_int, [P, P, c_int64, P, c_int64, c_int, P, P, P]),
+    "ptv3_pg_head_eval_capable": (c_int, [c_int, c_int]),
+    "ptv3_pg_head_eval": (c_int, [P, P, c_int64, c_int, c_int, P, P, P, P, P, P, c_float, P, P, P, P, c_float, P, c_int,
+                                  P, P, P, P, P, P, P]),
+    "ptv3_pg_bias_loss_fwd": (c_int, [P, P, P, P, c_int64, c_int64, P, P]),
+    "ptv3_pg_bias_loss_bwd": (c_int, [P, P, P, P, P, c_int64, c_int64, P, P, P]),
+    "ptv3_pg_proposals": (c_int, [P, P, c_int, c_int64, P, c_int, P, P, c_int64, c_int64, c_int, c_int, P, P, P, P, P]),
 }
 
 

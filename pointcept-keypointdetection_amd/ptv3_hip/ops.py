@@ -2439,3 +2439,185 @@ def octree_dwconv(x, w, nbr, bn_scale, bn_shift):
     lib.check(lib.ptv3_octree_dwconv(_p(x), _p(w), _p(nbr), _p(bn_scale), _p(bn_shift), _p(out), n, c, _stream()),
               "ptv3_octree_dwconv")
     return out
+
+
+# ---------------------------------------------------------------------------------------------
+# PointGroup: ball query over a cell grid, on-device clustering, proposals (parity with
+# pointgroup_ops unpinned)
+# ---------------------------------------------------------------------------------------------
+def _pg_args(who, xyz, offsets):
+    _chk(xyz, "xyz", torch.float32, 2)
+    _chk(offsets, "offsets", torch.int32, 1)
+    if xyz.shape[1] != 3 or offsets.shape[0] < 2:
+        raise RuntimeError(f"{who}: xyz (n, 3) and offsets (scenes + 1) expected")
+    n = xyz.shape[0]
+    ws_bytes = lib.ptv3_pg_workspace_bytes(n)
+    return n, offsets.shape[0] - 1, torch.empty(ws_bytes, dtype=torch.uint8, device=xyz.device), ws_bytes
+
+
+def pg_ballquery_batch_p(xyz, batch_idxs, batch_offsets, radius):
+    """(idx (nActive) int32, start_len (n, 2) int32) of ptv3_pg_ballquery_batch_p: per point the rows of its scene with
+    d2 < radius^2 in ascending index, at most 1000; start = exclusive scan of the counts by point index.  batch_idxs
+    may be None.  One synchronisation (the total sizes idx)."""
+    n, b, ws, ws_bytes = _pg_args("pg_ballquery_batch_p", xyz, batch_offsets)
+    if batch_idxs is not None:
+        _chk(batch_idxs, "batch_idxs", torch.int32, 1)
+        if batch_idxs.shape[0] != n:
+            raise RuntimeError("pg_ballquery_batch_p: batch_idxs must have one entry per point")
+    start_len = torch.empty((n, 2), dtype=torch.int32, device=xyz.device)
+    total = ctypes.c_int64(0)
+    args = (_p(xyz), _p(batch_idxs), _p(batch_offsets), b, n, float(radius), _p(start_len))
+    lib.check(lib.ptv3_pg_ballquery_batch_p(*args, None, ctypes.byref(total), _p(ws), ws_bytes, _stream()),
+              "ptv3_pg_ballquery_batch_p (count)")
+    idx = torch.empty(total.value, dtype=torch.int32, device=xyz.device)
+    if total.value:
+        lib.check(lib.ptv3_pg_ballquery_batch_p(*args, _p(idx), ctypes.byref(total), _p(ws), ws_bytes, _stream()),
+                  "ptv3_pg_ballquery_batch_p (fill)")
+    return idx, start_len
+
+
+def pg_cluster(xyz, label, offsets, radius, min_points, propose_points=0):
+    """ptv3_pg_cluster: (cluster_idxs (sum, 2) int32, cluster_offsets (clusters + 1) int32, n_large) on the device, or
+    None when a point has more than 1000 neighbours (PTV3_PG_TRUNCATED: the union is not the reference's directed search
+    there; take pg_ballquery_batch_p + pg_bfs_cluster_host).  n_large: clusters with more than propose_points members.
+    One synchronisation."""
+    from .lib import PTV3_PG_TRUNCATED
+    n, b, ws, ws_bytes = _pg_args("pg_cluster", xyz, offsets)
+    _chk(label, "label", torch.int32, 1)
+    if label.shape[0] != n:
+        raise RuntimeError("pg_cluster: label must have one entry per point")
+    cluster_idxs = torch.empty((n, 2), dtype=torch.int32, device=xyz.device)
+    cluster_offsets = torch.empty(n + 1, dtype=torch.int32, device=xyz.device)
+    record = (ctypes.c_int32 * 4)()
+    rc = lib.ptv3_pg_cluster(_p(xyz), _p(label), _p(offsets), b, n, float(radius), int(min_points), int(propose_points),
+                             _p(cluster_idxs), _p(cluster_offsets), record, _p(ws), ws_bytes, _stream())
+    if rc == PTV3_PG_TRUNCATED:
+        return None
+    lib.check(rc, "ptv3_pg_cluster")
+    return cluster_idxs[:record[1]], cluster_offsets[:record[0] + 1], int(record[3])
+
+
+def pg_bfs_cluster_host(semantic_label, ball_query_idxs, start_len, threshold):
+    """ptv3_pg_bfs_cluster_host on CPU int32 tensors: (cluster_idxs (sum, 2), cluster_offsets (clusters + 1)), members in
+    the reference's discovery order.  Touches no GPU."""
+    for t, name, dim in ((semantic_label, "semantic_label", 1), (ball_query_idxs, "ball_query_idxs", 1),
+                         (start_len, "start_len", 2)):
+        if t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != dim:
+            raise RuntimeError(f"pg_bfs_cluster_host: {name} must be a contiguous {dim}-d CPU int32 tensor")
+    n = start_len.shape[0]
+    if semantic_label.shape[0] != n or start_len.shape[1] != 2:
+        raise RuntimeError("pg_bfs_cluster_host: semantic_label (n) and start_len (n, 2) expected")
+    cluster_idxs = torch.empty((n, 2), dtype=torch.int32)
+    cluster_offsets = torch.empty(n + 1, dtype=torch.int32)
+    counts = (ctypes.c_int32 * 2)()
+    rc = lib.ptv3_pg_bfs_cluster_host(_p(semantic_label), _p(ball_query_idxs), ball_query_idxs.shape[0], _p(start_len),
+                                      n, int(threshold), _p(cluster_idxs), _p(cluster_offsets), counts)
+    if rc != 0:
+        raise RuntimeError(f"ptv3_pg_bfs_cluster_host failed (code {rc}): "
+                           + ("a list or an entry points outside the arrays" if rc == 2 else "bad argument"))
+    return cluster_idxs[:counts[1]].clone(), cluster_offsets[:counts[0] + 1].clone()
+
+
+def pg_sort_members(cluster_idxs):
+    """The lists of pg_bfs_cluster_host with every cluster's members in ascending index (the order pg_cluster writes)."""
+    if cluster_idxs.shape[0] == 0:
+        return cluster_idxs
+    key = cluster_idxs[:, 0].long() * (int(cluster_idxs[:, 1].max()) + 1) + cluster_idxs[:, 1].long()
+    return cluster_idxs[torch.argsort(key)].contiguous()
+
+
+def pg_proposals(cluster_idxs, cluster_offsets, prob, segment_pred, propose_points, num_proposals, row_map=None):
+    """ptv3_pg_proposals: (pred_classes (P) int64, pred_scores (P) fp32, pred_masks (P, N) int32) on the device for the
+    clusters with more than propose_points members; num_proposals is their number, known to the caller."""
+    _chk(cluster_idxs, "cluster_idxs", torch.int32, 2)
+    _chk(cluster_offsets, "cluster_offsets", torch.int32, 1)
+    _chk(prob, "prob", torch.float32, 2)
+    _chk(segment_pred, "segment_pred", torch.int64, 1)
+    _chk(row_map, "row_map", torch.int64, 1)
+    n, c = prob.shape
+    nc = cluster_offsets.shape[0] - 1
+    if segment_pred.shape[0] != n or nc < 0 or (cluster_idxs.shape[0] and cluster_idxs.shape[1] != 2):
+        raise RuntimeError("pg_proposals: segment_pred (N), cluster_idxs (sum, 2), cluster_offsets (clusters + 1) expected")
+    p = int(num_proposals)
+    dev = prob.device
+    pred_classes = torch.empty(p, dtype=torch.int64, device=dev)
+    pred_scores = torch.empty(p, dtype=torch.float32, device=dev)
+    pred_masks = torch.empty((p, n), dtype=torch.int32, device=dev)
+    slot = torch.empty(max(nc, 1), dtype=torch.int32, device=dev)
+    lib.check(lib.ptv3_pg_proposals(_p(cluster_idxs), _p(cluster_offsets), nc, cluster_idxs.shape[0], _p(prob), c,
+                                    _p(segment_pred), _p(row_map), 0 if row_map is None else row_map.shape[0], n,
+                                    int(propose_points), p, _p(pred_classes), _p(pred_scores), _p(pred_masks), _p(slot),
+                                    _stream()), "ptv3_pg_proposals")
+    return pred_classes, pred_scores, pred_masks
+
+
+def pg_head_eval_capable(c, num_classes):
+    return bool(lib.ptv3_pg_head_eval_capable(int(c), int(num_classes)))
+
+
+def pg_head_eval(feat, coord, w1, b1, bn_weight, bn_bias, bn_mean, bn_var, bn_eps, w2, b2, w_seg, b_seg, voxel_size,
+                 ignore_index=()):
+    """ptv3_pg_head_eval, one launch: (bias_pred (N, 3), logit (N, K), prob (N, K), segment_pred (N) int64, center (N, 3),
+    keep (N) bool) from feat (N, C) fp32, C = 64 or 96, K <= 256; weights as torch holds them, BatchNorm by its running
+    statistics."""
+    _chk(feat, "feat", torch.float32, 2)
+    _chk(coord, "coord", torch.float32, 2)
+    n, c = feat.shape
+    k = w_seg.shape[0]
+    if not pg_head_eval_capable(c, k):
+        raise RuntimeError(f"pg_head_eval: C = {c} (64 or 96) with {k} classes (1 .. 256) is not built")
+    shapes = ((w1, (c, c)), (b1, (c,)), (bn_weight, (c,)), (bn_bias, (c,)), (bn_mean, (c,)), (bn_var, (c,)), (w2, (3, c)),
+              (b2, (3,)), (w_seg, (k, c)), (b_seg, (k,)))
+    for i, (t, shape) in enumerate(shapes):
+        _chk(t, f"pg_head_eval: parameter {i}", torch.float32)
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"pg_head_eval: parameter {i} has shape {tuple(t.shape)}, expected {shape}")
+    ignore = [int(v) for v in ignore_index]
+    if tuple(coord.shape) != (n, 3) or len(ignore) > 8:
+        raise RuntimeError("pg_head_eval: coord (N, 3) and at most 8 ignored classes expected")
+    dev = feat.device
+    bias_pred = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    center = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    logit = torch.empty((n, k), dtype=torch.float32, device=dev)
+    prob = torch.empty((n, k), dtype=torch.float32, device=dev)
+    segment_pred = torch.empty(n, dtype=torch.int64, device=dev)
+    keep = torch.empty(n, dtype=torch.uint8, device=dev)
+    ig = (ctypes.c_int * max(len(ignore), 1))(*ignore)
+    lib.check(lib.ptv3_pg_head_eval(_p(feat), _p(coord), n, c, k, _p(w1), _p(b1), _p(bn_weight), _p(bn_bias), _p(bn_mean),
+                                    _p(bn_var), float(bn_eps), _p(w2), _p(b2), _p(w_seg), _p(b_seg), float(voxel_size), ig,
+                                    len(ignore), _p(bias_pred), _p(logit), _p(prob), _p(segment_pred), _p(center),
+                                    _p(keep), _stream()), "ptv3_pg_head_eval")
+    return bias_pred, logit, prob, segment_pred, center, keep.bool()
+
+
+def _pg_loss_args(bias_pred, coord, centroid, instance):
+    for t, name in ((bias_pred, "bias_pred"), (coord, "coord"), (centroid, "instance_centroid")):
+        _chk(t, name, torch.float32, 2)
+        if tuple(t.shape) != (bias_pred.shape[0], 3):
+            raise RuntimeError(f"pg_bias_loss: {name} must be (N, 3)")
+    _chk(instance, "instance", torch.int64, 1)
+    if instance.shape[0] != bias_pred.shape[0]:
+        raise RuntimeError("pg_bias_loss: instance must have one entry per point")
+
+
+def pg_bias_loss(bias_pred, coord, centroid, instance, ignore_index=-1):
+    """ptv3_pg_bias_loss_fwd: out (3) fp32 = masked L1 loss, masked negative-cosine loss, their denominator."""
+    _pg_loss_args(bias_pred, coord, centroid, instance)
+    out = torch.empty(3, dtype=torch.float32, device=bias_pred.device)
+    lib.check(lib.ptv3_pg_bias_loss_fwd(_p(bias_pred), _p(coord), _p(centroid), _p(instance), int(ignore_index),
+                                        bias_pred.shape[0], _p(out), _stream()), "ptv3_pg_bias_loss_fwd")
+    return out
+
+
+def pg_bias_loss_bwd(dloss, bias_pred, coord, centroid, instance, fwd_out, ignore_index=-1):
+    """ptv3_pg_bias_loss_bwd: d bias_pred (N, 3) from dloss (2) = the gradients of the two losses."""
+    _pg_loss_args(bias_pred, coord, centroid, instance)
+    _chk(dloss, "dloss", torch.float32, 1)
+    _chk(fwd_out, "fwd_out", torch.float32, 1)
+    if dloss.shape[0] != 2 or fwd_out.shape[0] != 3:
+        raise RuntimeError("pg_bias_loss_bwd: dloss (2) and the forward's out (3) expected")
+    dbias = torch.empty_like(bias_pred)
+    lib.check(lib.ptv3_pg_bias_loss_bwd(_p(dloss), _p(bias_pred), _p(coord), _p(centroid), _p(instance),
+                                        int(ignore_index), bias_pred.shape[0], _p(fwd_out), _p(dbias), _stream()),
+              "ptv3_pg_bias_loss_bwd")
+    return dbias
