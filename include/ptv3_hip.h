@@ -189,6 +189,18 @@ int ptv3_gemm(const void* x, const void* w, void* out, int64_t m, int cin, int c
               const float* bn_shift, int act, const void* res, const int32_t* res_index, void* out2,
               int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- k^3 stem convolution straight from the block table -------------------------------------------------
+ * ptv3_gemm(x, w, out, n, cin, cout, k^3, nbr = the table ptv3_subm_neighbors_blocks(indices, n, table, ksize) gives,
+ * row_order, bias, bn_scale, bn_shift, act, no residual, dtype, its workspace) without that (n, k^3) table: a tile of 64
+ * sites resolves its neighbour rows from `table` (ptv3_subm_build_block_table[_zeroed] over the same indices and n)
+ * into LDS and runs ptv3_gemm's 64-point tile over them.  out is byte-equal to that call in fp32 and bf16, K split
+ * included.  ksize 5 (the PTv3 stem) or 3; duplicate coordinates as in the table: the smallest row is the neighbour,
+ * every row gets its own output.  x (n, cin), w (cout, ksize^3, cin), out (n, cout) in dtype; indices 16-byte aligned. */
+int ptv3_stem_conv_blocks(const void* x, const void* w, void* out, int64_t n, int cin, int cout, int ksize,
+                          const int32_t* indices, const void* table, size_t table_bytes, const int32_t* row_order,
+                          const float* bias, const float* bn_scale, const float* bn_shift, int act, int dtype,
+                          void* stream);
+
 /* ---- narrow 3^3 convolution with the tile's neighbour rows held in LDS --------------------------------
  * ptv3_gemm gathers the rows of x once per tap.  For cin = cout = c in {32, 64} and kvol = 27 the rows a tile of
  * consecutive sites needs can be fetched once instead: ptv3_halo_plan_build cuts the m sites, in row_order, into tiles

@@ -133,7 +133,7 @@ struct Level {
   const int64_t* grid = nullptr; const int64_t* batch = nullptr;
   int64_t *code = nullptr, *order = nullptr, *inverse = nullptr;
   int32_t* indices = nullptr; void* table = nullptr; size_t table_bytes = 0;   // table of 4^3 blocks (sparse.hip)
-  int32_t* nbr3 = nullptr; int32_t* nbr5 = nullptr; int32_t* row_order = nullptr;
+  int32_t* nbr3 = nullptr; int32_t* row_order = nullptr;
   // halo plan of nbr3 in row_order (ptv3_halo_plan_build) where a conv of the level takes it; built BEHIND `ready`
   void* halo = nullptr; size_t halo_bytes = 0; hipEvent_t halo_ready = nullptr; bool halo_waited = false;
   Plan plan[2];                 // [0] encoder patch, [1] decoder patch (shared when K is equal)
@@ -365,7 +365,8 @@ struct Run {
   }
 
   hipEvent_t stem_ready = nullptr;
-  // Level 0, the part that needs coordinates and batch ids only: sites, block table, 5^3 table.  It is queued before
+  // Level 0, the part that needs coordinates and batch ids only: sites and block table; the stem conv resolves its 5^3
+  // neighbourhoods from that table itself (ptv3_stem_conv_blocks) and may start behind it.  All of it is queued before
   // the host has read the depth and the offsets back, so it runs while the host waits.  One launch converts the sites
   // and zero-fills the table (ptv3_subm_sites); row_order is written later, by the last pass of the sort.
   void level0_sites(Level& L, const void* grid_in, int is_i64) {
@@ -377,8 +378,7 @@ struct Run {
     L.table = G->alloc(L.table_bytes);
     RUN(ptv3_subm_sites(L.batch, grid_in, is_i64, L.n, L.indices, g64, L.table, L.table_bytes, sg));
     RUN(ptv3_subm_build_block_table_zeroed(L.indices, L.n, L.table, L.table_bytes, sg));
-    L.nbr5 = (int32_t*)G->alloc((size_t)L.n * 125 * 4);
-    RUN(ptv3_subm_neighbors_blocks(L.indices, L.n, L.table, L.table_bytes, 5, L.nbr5, sg));
+    if (!dry && ok()) { stem_ready = X->event_at(19); (void)hipEventRecord(stem_ready, sg); }
   }
 
   // 3^3 table and window plans of one level whose sites and block table exist
@@ -561,13 +561,16 @@ static int run_forward(Exec* X, const ptv3_model_desc* d, const void* const* par
   // Order on the geometry stream: coordinate maximum, whose last workgroup writes the maximum and the offsets into the
   // executor's pinned buffer (a copy only where the depth is given and the offsets are not), and an event; then
   // everything of level 0 that needs neither the depth nor validated offsets (batch ids, sites + table zero fill, block
-  // table, 5^3 table); the host waits for the event alone and validates; then curve codes and the sort, whose last pass
-  // leaves row_order: the stem conv may start; then the 3^3 table and the window plans.
+  // table) and, on the feature stream behind the table's event, the stem conv; the host waits for the read-back event
+  // alone and validates; then curve codes and the sort, whose last pass leaves row_order; then the 3^3 table and the
+  // window plans.
   // The kernels queued ahead of the validation run for ANY int32 coordinates and any offsets, and a failed validation
   // returns with them in flight; they stay inside this call's arena: batch_from_offset_kernel and bt_sites_kernel index by
   // the point (< n) and read offset[0 .. b) only; the block-table kernels reach the slots through `& smask`, a bit
-  // through `& 3` fields, the payload through base + rank < (bits set) <= n (sparse.hip), and bt_neighbors_kernel
-  // range-checks every tap before it looks anything up and writes n x 125 entries by position.
+  // through `& 3` fields, the payload through base + rank < (bits set) <= n (sparse.hip).  The stem conv
+  // (conv_stem.hip) range-checks every tap before it looks anything up; its neighbour rows come from base + rank < n of a
+  // slot whose key matched and whose bit is set (clamped to the payload besides), and every payload entry is ~row of a
+  // row < n, so it reads `feat` at rows < n only; it writes n x C0 by position inside this call's feature arena.
   const int* hmax = nullptr; const int64_t* hoff = nullptr;
   hipEvent_t read_back = nullptr;
   if (dry) {
@@ -601,6 +604,26 @@ static int run_forward(Exec* X, const ptv3_model_desc* d, const void* const* par
     L0.batch = bt;
   }
   R.level0_sites(L0, io->grid_coord, io->coord_is_i64);
+  // ---------------- the stem conv needs the block table only: it is queued before the host blocks on the read-back and
+  // runs on the feature stream beside the sort.  Parameter walk order (header): stem, enc stage 0 blocks, [down, blocks]
+  // ..., decoder, head.
+  const void* stem_w = R.next(); const float* stem_s = (const float*)R.next(); const float* stem_t = (const float*)R.next();
+  {
+    if (!dry && R.ok()) (void)hipStreamWaitEvent(sf, R.stem_ready, 0);
+    const int C0 = d->enc_channels[0];
+    L0.feat = F.alloc((size_t)L0.n * C0 * es); L0.channels = C0;
+    const void* feat_in = io->feat;
+    if (io->raw_feat) {
+      // overlap mode: pad + cast the caller's features here, on the executor's stream (no producer on `stream`)
+      void* padded = F.alloc((size_t)L0.n * d->in_channels * es);
+      if (!dry && R.ok())
+        pad_cast(io->raw_feat, io->raw_feat_dtype, io->raw_feat_channels, padded, d->dtype, d->in_channels, L0.n, sf);
+      feat_in = padded;
+    }
+    RUNR(ptv3_stem_conv_blocks(feat_in, stem_w, L0.feat, L0.n, d->in_channels, C0, 5, L0.indices, L0.table, L0.table_bytes,
+                               nullptr, nullptr, stem_s, stem_t, PTV3_ACT_GELU, d->dtype, sf));
+    L0.conv_feat = L0.feat;
+  }
   if (!dry) {
     if (read_back && X->timed_event_sync(read_back) != hipSuccess) {
       set_error("forward: input read-back failed");
@@ -623,8 +646,6 @@ static int run_forward(Exec* X, const ptv3_model_desc* d, const void* const* par
     RUNR(ptv3_argsort_i64_rows(L0.code, k, io->n, std::max(1, 3 * depth + nbits), L0.order, L0.inverse, L0.row_order, ws, wsb,
                                sg));
   }
-  // the stem conv needs the 5^3 table and the row order only: it starts here, under the 3^3 table and the window plans
-  if (!dry && R.ok()) { R.stem_ready = X->event_at(19); (void)hipEventRecord(R.stem_ready, sg); }
   R.level_tables(L0, 0);
   if (io->stage_points_host) io->stage_points_host[0] = L0.n;
   if (!dry && R.ok()) { L0.ready = X->event_at(1); (void)hipEventRecord(L0.ready, sg); }
@@ -633,25 +654,7 @@ static int run_forward(Exec* X, const ptv3_model_desc* d, const void* const* par
   // ---------------- features of level 0 start as soon as its geometry is queued
   auto wait_level = [&](Level& L) { if (!dry && R.ok()) (void)hipStreamWaitEvent(sf, L.ready, 0); };
   struct PoolParams { const void* w; const float *b, *bns, *bnt; };
-  // parameter walk order (header): stem, enc stage 0 blocks, [down, blocks] ..., decoder, head.
-  const void* stem_w = R.next(); const float* stem_s = (const float*)R.next(); const float* stem_t = (const float*)R.next();
-  {
-    if (!dry && R.ok()) (void)hipStreamWaitEvent(sf, R.stem_ready, 0);
-    const int C0 = d->enc_channels[0];
-    L0.feat = F.alloc((size_t)L0.n * C0 * es); L0.channels = C0;
-    const void* feat_in = io->feat;
-    if (io->raw_feat) {
-      // overlap mode: pad + cast the caller's features here, on the executor's stream (no producer on `stream`)
-      void* padded = F.alloc((size_t)L0.n * d->in_channels * es);
-      if (!dry && R.ok())
-        pad_cast(io->raw_feat, io->raw_feat_dtype, io->raw_feat_channels, padded, d->dtype, d->in_channels, L0.n, sf);
-      feat_in = padded;
-    }
-    R.gemm(feat_in, stem_w, L0.feat, L0.n, d->in_channels, C0, 125, L0.nbr5, L0.row_order, nullptr, stem_s, stem_t,
-           PTV3_ACT_GELU, nullptr, nullptr, nullptr);
-    L0.conv_feat = L0.feat;
-    wait_level(L0);    // the blocks need the 3^3 table and the window plans
-  }
+  wait_level(L0);    // the blocks need the 3^3 table and the window plans
   for (int st = 0; st < S; ++st) {
     Level& L = lv[st];
     if (st > 0) {

@@ -80,6 +80,8 @@ SIGNATURES = {
     "ptv3_gemm": (c_int, [P, P, P, c_int64, c_int, c_int, c_int, P, P, P, P, P, c_int, P, P, P, c_int, P, c_size_t,
                           P]),
     "ptv3_gemm_splits": (c_int, [c_int64, c_int, c_int, c_int, c_int]),
+    "ptv3_stem_conv_blocks": (c_int, [P, P, P, c_int64, c_int, c_int, c_int, P, P, c_size_t, P, P, P, P, c_int, c_int,
+                                      P]),
     "ptv3_halo_plan_bytes": (c_size_t, [c_int64]),
     "ptv3_halo_plan_shape": (c_int, [P, P]),
     "ptv3_halo_plan_build": (c_int, [P, P, c_int64, P, c_size_t, P]),

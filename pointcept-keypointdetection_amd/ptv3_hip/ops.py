@@ -396,6 +396,40 @@ def gemm(x, w, bias=None, nbr=None, kvol=1, row_order=None, bn_scale=None, bn_sh
     return (out, out2) if dual else out
 
 
+def stem_conv_blocks(x, w, indices, table, ksize=5, bias=None, row_order=None, bn_scale=None, bn_shift=None, act=ACT_NONE,
+                     out=None):
+    """gemm(x, w, nbr=subm_neighbors_blocks(indices, ksize, table)[0], kvol=ksize^3, ...) without the neighbour table
+    (ptv3_stem_conv_blocks): a tile resolves its neighbour rows from the block table into LDS.  Byte-equal to that call.
+    out: an (n, cout) tensor to write into (tests pre-fill it to see a skipped store)."""
+    _chk(x, "x", (torch.float32, torch.bfloat16), 2)
+    _chk(w, "w", x.dtype)
+    for t, nm in ((bias, "bias"), (bn_scale, "bn_scale"), (bn_shift, "bn_shift")):
+        _chk(t, nm, torch.float32, 1)
+    _chk(indices, "indices", torch.int32, 2)
+    _chk(table, "table", torch.uint8, 1)
+    _chk(row_order, "row_order", torch.int32, 1)
+    n, cin = x.shape
+    cout = w.shape[0]
+    if indices.shape[0] != n or indices.shape[1] != 4:
+        raise RuntimeError("stem_conv_blocks: indices must be (n, 4) for the n rows of x")
+    if w.numel() != cout * int(ksize) ** 3 * cin:
+        raise RuntimeError(f"stem_conv_blocks: weight has {w.numel()} elements, expected {cout}x{int(ksize) ** 3}x{cin}")
+    for t in (bias, bn_scale, bn_shift):
+        if t is not None and t.numel() != cout:
+            raise RuntimeError("stem_conv_blocks: epilogue vector length != cout")
+    if row_order is not None and row_order.shape[0] != n:
+        raise RuntimeError("stem_conv_blocks: row_order length != n")
+    if out is None:
+        out = torch.empty((n, cout), dtype=x.dtype, device=x.device)
+    _chk(out, "out", x.dtype, 2)
+    if tuple(out.shape) != (n, cout):
+        raise RuntimeError("stem_conv_blocks: out must be (n, cout)")
+    lib.check(lib.ptv3_stem_conv_blocks(_p(x), _p(w), _p(out), n, cin, cout, int(ksize), _p(indices), _p(table),
+                                        table.numel(), _p(row_order), _p(bias), _p(bn_scale), _p(bn_shift), int(act),
+                                        _dt(x), _stream()), "ptv3_stem_conv_blocks")
+    return out
+
+
 def halo_plan_shape():
     """(T, CAP): sites per tile and the most distinct neighbour rows a tile may have on the fast path."""
     t, cap = ctypes.c_int(0), ctypes.c_int(0)
