@@ -1228,6 +1228,46 @@ int ptv3_pg_bias_loss_bwd(const float* dloss, const float* bias_pred, const floa
                           const int64_t* instance, int64_t ignore_index, int64_t n, const float* fwd_out, float* dbias,
                           void* stream);
 
+/* Head of the context-aware classifier, pointcept/models/context_aware_classifier/context_aware_classifier_v1m1_base.py
+ * (csrc/cac.hip).  All tensors fp32 row-major, labels int64, offset (nb) int64 cumulative scene ends.  No atomics: two
+ * runs are bitwise equal.  Nothing is read back by the host.
+ * ptv3_cac_capable: the (K classes, C channels) the kernels cover: 2 <= K <= 256, 1 <= C <= 128 and every kernel's LDS
+ *   need (the largest is 4 * (Kp * (C + 1) + 32 * (C + 1 + Kp)) bytes, Kp = K rounded up to 4) within 144 KiB.
+ * ptv3_cac_proto_fwd: class prototypes, two weightings behind one accumulation scheme.
+ *   logits != NULL (softmax form, :131-142 per scene of post_refine_proto_batch): p = softmax(logits[i]); with
+ *     conf_thresh > 0 a point whose largest p is below it contributes nothing; proto (nb, K, C) =
+ *     sum_i p[i, k] x[i] / (sum_i p[i, k] + 1e-7) over the points of a scene; den (nb, K) = sum_i p[i, k].
+ *   labels != NULL (label form, :78-90 of get_adaptive_perspective, whole batch, offset and nb ignored): proto (1, K, C)
+ *     = sum_{t_i = k} x[i] / (count_k + 1e-4); den (K) = count_k as fp32, count (K) int32.  A label outside [0, K) is
+ *     ignored (-1 is the reference's).  A class is present when count_k > 0: no unique().
+ *   A workgroup takes 2048 rows that never straddle a scene, the chunks of a scene are added in increasing order in
+ *   float64.  workspace: ptv3_cac_proto_workspace_bytes(n, K, C, nb).  Rows past offset[nb - 1] belong to no scene.
+ * ptv3_cac_proto_bwd: dx (n, C) = sum_k w[i, k] dproto[b, k] / (den[b, k] + eps), the weights recomputed (the logits
+ *   carry no gradient: detach_pre_logits=True).  Rows that belong to no scene are not written.
+ * ptv3_cac_cos_logits_fwd: get_pred (:66-71) times temp per scene: out (n, K) = temp * <y_i / max(|y_i|, 1e-12),
+ *   q[b, k] / max(|q[b, k]|, 1e-12)>; q (nb, K, C), or (1, K, C) for every row with shared != 0 (offset ignored).  The
+ *   normalised rows stay in LDS.  Forward only: training composes get_pred in torch.
+ * ptv3_cac_distill_fwd: get_distill_loss (:153-199) at smoothness 0.5, eps 0.  out[0] = the loss (0 when no label lies
+ *   in [0, K)), coef (K) = the backward's per-class factor 1 / ((n_present + 1e-4)(sum entropy_k + 1e-4)), count (K + 1)
+ *   int32 = valid rows per class, then n_present.  An ignored row takes class 0 in the smoothed label as the
+ *   reference's onehot * (1 - ignore_mask) does, and weighs nothing.  workspace: ptv3_cac_distill_workspace_bytes(n, K).
+ * ptv3_cac_distill_bwd: dpred (n, K) in one launch; `soft` carries no gradient (:158). */
+int ptv3_cac_capable(int K, int C);
+size_t ptv3_cac_proto_workspace_bytes(int64_t n, int K, int C, int nb);
+int ptv3_cac_proto_fwd(const float* x, const float* logits, const int64_t* labels, const int64_t* offset, int nb,
+                       int64_t n, int K, int C, float conf_thresh, float* proto, float* den, int32_t* count,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int ptv3_cac_proto_bwd(const float* dproto, const float* den, const float* logits, const int64_t* labels,
+                       const int64_t* offset, int nb, int64_t n, int K, int C, float conf_thresh, float* dx,
+                       void* stream);
+int ptv3_cac_cos_logits_fwd(const float* y, const float* q, const int64_t* offset, int nb, int64_t n, int K, int C,
+                            int shared, float temp, float* out, void* stream);
+size_t ptv3_cac_distill_workspace_bytes(int64_t n, int K);
+int ptv3_cac_distill_fwd(const float* pred, const float* soft, const int64_t* labels, int64_t n, int K, float* out,
+                         float* coef, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+int ptv3_cac_distill_bwd(const float* dloss, const float* pred, const float* soft, const int64_t* labels,
+                         const float* coef, int64_t n, int K, float* dpred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -522,6 +522,65 @@ def focal_loss(logits, labels, alpha, gamma=2.0, ignore_index=-1, loss_weight=1.
     return FocalLossFn.apply(logits, labels, alpha, gamma, ignore_index, loss_weight, reduction)
 
 
+class CacProtoFn(Function):
+    """Class prototypes of the context-aware classifier (ops.cac_proto): the gradient goes to x alone - the logits
+    arrive detached (detach_pre_logits=True) and labels carry none.  Saved: the weights' source and the denominators;
+    the weights themselves are recomputed by the backward launch."""
+
+    @staticmethod
+    def forward(ctx, x, logits, labels, offset, num_classes, conf_thresh):
+        x = x.contiguous()
+        logits = None if logits is None else logits.contiguous()
+        labels = None if labels is None else labels.contiguous()
+        off = None if logits is None else ops._scene_offset(offset, "offset")
+        proto, den, count = ops.cac_proto(x, logits, labels, off, num_classes, conf_thresh)
+        ctx.save_for_backward(logits, labels, off, den)
+        ctx.x_shape, ctx.conf_thresh = tuple(x.shape), conf_thresh
+        if count is None:
+            ctx.mark_non_differentiable(den)
+            return proto, den
+        ctx.mark_non_differentiable(den, count)
+        return proto, den, count
+
+    @staticmethod
+    def backward(ctx, dproto, *_):
+        logits, labels, off, den = ctx.saved_tensors
+        dx = ops.cac_proto_bwd(dproto.float().contiguous(), den, ctx.x_shape, logits, labels, off, ctx.conf_thresh)
+        return dx, None, None, None, None, None
+
+
+def cac_proto_softmax(x, logits, offset, conf_thresh=0.0):
+    """-> (proto (B, K, C) with grad to x, den (B, K)); logits are taken as constants."""
+    return CacProtoFn.apply(x, logits.detach(), None, offset, None, conf_thresh)
+
+
+def cac_proto_label(x, labels, num_classes):
+    """-> (proto (K, C) with grad to x, den (K) fp32, count (K) int32)."""
+    return CacProtoFn.apply(x, None, labels, None, num_classes, 0.0)
+
+
+class CacDistillFn(Function):
+    """get_distill_loss at its defaults on fp32 (N, K) logits: two launches forward, one backward; the gradient goes to
+    `pred` alone (`soft` is detached by the reference).  Saved besides the inputs: the per-class factor."""
+
+    @staticmethod
+    def forward(ctx, pred, soft, labels):
+        pred, soft, labels = pred.contiguous(), soft.contiguous(), labels.contiguous()
+        out, coef, _count = ops.cac_distill(pred, soft, labels)
+        ctx.save_for_backward(pred, soft, labels, coef)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        pred, soft, labels, coef = ctx.saved_tensors
+        return ops.cac_distill_bwd(dloss.float().contiguous().view(1), pred, soft, labels, coef), None, None
+
+
+def cac_distill(pred, soft, labels):
+    """-> loss, 0-d fp32 with grad to pred."""
+    return CacDistillFn.apply(pred, soft.detach(), labels)
+
+
 def linear(x, weight, bias=None):
     return LinearFn.apply(x, weight, bias)
 

@@ -202,3 +202,27 @@ PG_SPUNET_SCANNET_CFG = dict(
                   layers=(2, 3, 4, 6, 2, 2, 2, 2)),
     backbone_out_channels=96, **_PG_SCANNET,
 )
+
+# Context-aware classifier: the `model` dicts of configs/scannet/semseg-cac-v1m1-1-spunet-lovasz.py:10-33 and
+# configs/scannet200/semseg-cac-v1m1-2-ptv2-lovasz.py:14-57
+_CAC_CRITERIA = [dict(type="CrossEntropyLoss", loss_weight=1.0, ignore_index=-1),
+                 dict(type="LovaszLoss", mode="multiclass", loss_weight=1.0, ignore_index=-1)]
+CAC_SPUNET_SCANNET_CFG = dict(
+    type="CAC-v1m1",
+    backbone=dict(type="SpUNet-v1m1", in_channels=6, num_classes=0, channels=(32, 64, 128, 256, 256, 128, 96, 96),
+                  layers=(2, 3, 4, 6, 2, 2, 2, 2)),
+    criteria=_CAC_CRITERIA, num_classes=20, backbone_out_channels=96, cos_temp=15, main_weight=1, pre_weight=1,
+    pre_self_weight=1, kl_weight=1, conf_thresh=0.75, detach_pre_logits=True,
+)
+CAC_PTV2_SCANNET200_CFG = dict(
+    type="CAC-v1m1",
+    backbone=dict(
+        type="PT-v2m2", in_channels=9, num_classes=0, patch_embed_depth=1, patch_embed_channels=48,
+        patch_embed_groups=6, patch_embed_neighbours=8, enc_depths=(2, 2, 6, 2), enc_channels=(96, 192, 384, 512),
+        enc_groups=(12, 24, 48, 64), enc_neighbours=(16, 16, 16, 16), dec_depths=(1, 1, 1, 1),
+        dec_channels=(48, 96, 192, 384), dec_groups=(6, 12, 24, 48), dec_neighbours=(16, 16, 16, 16),
+        grid_sizes=(0.06, 0.15, 0.375, 0.9375), attn_qkv_bias=True, pe_multiplier=False, pe_bias=True,
+        attn_drop_rate=0.0, drop_path_rate=0.3, enable_checkpoint=False, unpool_backend="map"),
+    criteria=_CAC_CRITERIA, num_classes=200, backbone_out_channels=48, cos_temp=15, main_weight=1, pre_weight=1,
+    pre_self_weight=1, kl_weight=1, conf_thresh=0, detach_pre_logits=True,
+)

@@ -238,6 +238,14 @@ SIGNATURES = {
     "ptv3_pg_bias_loss_fwd": (c_int, [P, P, P, P, c_int64, c_int64, P, P]),
     "ptv3_pg_bias_loss_bwd": (c_int, [P, P, P, P, P, c_int64, c_int64, P, P, P]),
     "ptv3_pg_proposals": (c_int, [P, P, c_int, c_int64, P, c_int, P, P, c_int64, c_int64, c_int, c_int, P, P, P, P, P]),
+    "ptv3_cac_capable": (c_int, [c_int, c_int]),
+    "ptv3_cac_proto_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "ptv3_cac_proto_fwd": (c_int, [P, P, P, P, c_int, c_int64, c_int, c_int, c_float, P, P, P, P, c_size_t, P]),
+    "ptv3_cac_proto_bwd": (c_int, [P, P, P, P, P, c_int, c_int64, c_int, c_int, c_float, P, P]),
+    "ptv3_cac_cos_logits_fwd": (c_int, [P, P, P, c_int, c_int64, c_int, c_int, c_int, c_float, P, P]),
+    "ptv3_cac_distill_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "ptv3_cac_distill_fwd": (c_int, [P, P, P, c_int64, c_int, P, P, P, P, c_size_t, P]),
+    "ptv3_cac_distill_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P, P]),
 }
 
 

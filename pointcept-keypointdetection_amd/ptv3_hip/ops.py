@@ -1564,6 +1564,129 @@ def focal_loss_bwd(dloss, logits, labels, alpha, nvalid, gamma=2.0, ignore_index
 
 
 # ---------------------------------------------------------------------------------------------
+# context-aware classifier head (csrc/cac.hip)
+# ---------------------------------------------------------------------------------------------
+def cac_capable(k, c):
+    """(K classes, C channels) ptv3_cac_* cover: 2 <= K <= 256, 1 <= C <= 128 and the LDS need within 144 KiB (the six
+    shapes of the semseg-cac-v1m1 configs - C 48 / 96, K 20 / 100 / 200 - lie inside)."""
+    return bool(lib.ptv3_cac_capable(int(k), int(c)))
+
+
+def _cac_proto_args(who, x, logits, labels, offset):
+    _chk(x, f"{who}: x", torch.float32, 2)
+    n, c = x.shape
+    if (logits is None) == (labels is None):
+        raise RuntimeError(f"{who}: give logits (softmax weights, per scene) or labels (whole batch)")
+    if logits is not None:
+        _chk(logits, f"{who}: logits", torch.float32, 2)
+        if logits.shape[0] != n:
+            raise RuntimeError(f"{who}: x {tuple(x.shape)} / logits {tuple(logits.shape)}: expected (N, C), (N, K)")
+        off = _scene_offset(offset, "offset")
+        return n, c, logits.shape[1], off, off.shape[0]
+    _chk(labels, f"{who}: labels", torch.int64, 1)
+    if labels.shape[0] != n:
+        raise RuntimeError(f"{who}: x {tuple(x.shape)} / labels {tuple(labels.shape)}: expected (N, C), (N)")
+    return n, c, None, None, 1
+
+
+def cac_proto(x, logits=None, labels=None, offset=None, num_classes=None, conf_thresh=0.0):
+    """Class prototypes.  logits (N, K) + offset: (proto (B, K, C), den (B, K), None), the confidence-masked softmax
+    weighting of post_refine_proto_batch per scene.  labels (N) + num_classes: (proto (K, C), den (K), count (K) int32),
+    the label weighting of get_adaptive_perspective over the whole batch."""
+    n, c, k, off, b = _cac_proto_args("cac_proto", x, logits, labels, offset)
+    k = int(num_classes) if k is None else k
+    dev = x.device
+    proto = torch.empty((b, k, c), dtype=torch.float32, device=dev)
+    den = torch.empty((b, k), dtype=torch.float32, device=dev)
+    count = torch.empty(k, dtype=torch.int32, device=dev) if labels is not None else None
+    nbytes = lib.ptv3_cac_proto_workspace_bytes(n, k, c, b)
+    ws = _ws(nbytes, dev)
+    lib.check(lib.ptv3_cac_proto_fwd(_p(x), _p(logits), _p(labels), _p(off), b, n, k, c, float(conf_thresh), _p(proto),
+                                     _p(den), _p(count), _p(ws), nbytes, _stream()), "ptv3_cac_proto_fwd")
+    if labels is not None:
+        return proto[0], den[0], count
+    return proto, den, None
+
+
+def cac_proto_bwd(dproto, den, x_shape, logits=None, labels=None, offset=None, conf_thresh=0.0):
+    """dx (N, C) of cac_proto; the weights are recomputed from logits / labels."""
+    n, c = x_shape
+    _chk(dproto, "dproto", torch.float32)
+    _chk(den, "den", torch.float32)
+    k = den.shape[-1]
+    off, b = None, 1
+    if logits is not None:
+        _chk(logits, "logits", torch.float32, 2)
+        off = _scene_offset(offset, "offset")
+        b = off.shape[0]
+        if tuple(logits.shape) != (n, k):
+            raise RuntimeError("cac_proto_bwd: logits must be (N, K)")
+    else:
+        _chk(labels, "labels", torch.int64, 1)
+        if labels.shape[0] != n:
+            raise RuntimeError("cac_proto_bwd: labels must be (N)")
+    if dproto.numel() != b * k * c or den.numel() != b * k:
+        raise RuntimeError("cac_proto_bwd: dproto must be (B, K, C) and den (B, K)")
+    dx = torch.zeros((n, c), dtype=torch.float32, device=dproto.device)
+    lib.check(lib.ptv3_cac_proto_bwd(_p(dproto), _p(den), _p(logits), _p(labels), _p(off), b, n, k, c,
+                                     float(conf_thresh), _p(dx), _stream()), "ptv3_cac_proto_bwd")
+    return dx
+
+
+def cac_cos_logits(y, q, offset=None, temp=1.0):
+    """temp * get_pred(y, q) -> (N, K).  q (B, K, C) with offset: per scene; q (K, C) or (1, K, C): shared."""
+    _chk(y, "y", torch.float32, 2)
+    _chk(q, "q", torch.float32)
+    n, c = y.shape
+    shared = q.dim() == 2 or offset is None
+    if q.dim() not in (2, 3) or q.shape[-1] != c or (shared and q.dim() == 3 and q.shape[0] != 1):
+        raise RuntimeError(f"cac_cos_logits: y {tuple(y.shape)} / q {tuple(q.shape)}: expected (N, C) and (B, K, C) or (K, C)")
+    k = q.shape[-2]
+    off, b = None, 1
+    if not shared:
+        off = _scene_offset(offset, "offset")
+        b = off.shape[0]
+        if q.shape[0] != b:
+            raise RuntimeError(f"cac_cos_logits: q holds {q.shape[0]} scenes, offset {b}")
+    out = torch.zeros((n, k), dtype=torch.float32, device=y.device) if not shared else \
+        torch.empty((n, k), dtype=torch.float32, device=y.device)
+    lib.check(lib.ptv3_cac_cos_logits_fwd(_p(y), _p(q), _p(off), b, n, k, c, int(shared), float(temp), _p(out),
+                                          _stream()), "ptv3_cac_cos_logits_fwd")
+    return out
+
+
+def cac_distill(pred, soft, labels):
+    """get_distill_loss at its defaults -> (out (1) fp32 = the loss, coef (K) fp32, count (K + 1) int32)."""
+    n, k = _seg_args("cac_distill", pred, labels)
+    _chk(soft, "soft", torch.float32, 2)
+    if tuple(soft.shape) != (n, k):
+        raise RuntimeError("cac_distill: pred and soft must have one shape")
+    dev = pred.device
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    coef = torch.empty(k, dtype=torch.float32, device=dev)
+    count = torch.empty(k + 1, dtype=torch.int32, device=dev)
+    nbytes = lib.ptv3_cac_distill_workspace_bytes(n, k)
+    ws = _ws(nbytes, dev)
+    lib.check(lib.ptv3_cac_distill_fwd(_p(pred), _p(soft), _p(labels), n, k, _p(out), _p(coef), _p(count), _p(ws),
+                                       nbytes, _stream()), "ptv3_cac_distill_fwd")
+    return out, coef, count
+
+
+def cac_distill_bwd(dloss, pred, soft, labels, coef):
+    """dpred (N, K) fp32 of cac_distill."""
+    n, k = _seg_args("cac_distill_bwd", pred, labels)
+    _chk(soft, "soft", torch.float32, 2)
+    _chk(dloss, "dloss", torch.float32)
+    _chk(coef, "coef", torch.float32, 1)
+    if tuple(soft.shape) != (n, k) or dloss.numel() != 1 or coef.shape[0] != k:
+        raise RuntimeError("cac_distill_bwd: soft must be (N, K), dloss hold one value and coef K")
+    dpred = torch.empty_like(pred)
+    lib.check(lib.ptv3_cac_distill_bwd(_p(dloss), _p(pred), _p(soft), _p(labels), _p(coef), n, k, _p(dpred), _stream()),
+              "ptv3_cac_distill_bwd")
+    return dpred
+
+
+# ---------------------------------------------------------------------------------------------
 # pointops
 # ---------------------------------------------------------------------------------------------
 def knn_query(nsample, xyz, offset, new_xyz, new_offset):
