@@ -1268,6 +1268,23 @@ int ptv3_cac_distill_fwd(const float* pred, const float* soft, const int64_t* la
 int ptv3_cac_distill_bwd(const float* dloss, const float* pred, const float* soft, const int64_t* labels,
                          const float* coef, int64_t n, int K, float* dpred, void* stream);
 
+/* Language-guided head of Point Prompt Training in eval, pointcept/models/point_prompt_training/
+ * point_prompt_training_v1m1_language_guided.py:98-107 (csrc/ppt_head.hip): h = W x + b (D wide, CLIP's text space),
+ * seg_logits = exp(logit_scale) * (h / |h|) . E_v^T over the K valid class embeddings.  Nothing nonlinear lies between W
+ * and E_v, so the caller collapses them once per weights (ptv3_hip.ops.ppt_head_collapse, float64 on the host, rounded
+ * once): with the thin factorisation W = Q R, q = Q^T b, beta = |b - Q q|^2, M = W^T E_v^T, c = E_v b
+ *   |h|^2 = |R x + q|^2 + beta (still a sum of squares; the Gram form x^T W^T W x loses half the digits and is not used),
+ *   h . e_k = (M^T x + c)_k.
+ * ptv3_ppt_head_fwd: x (n, C) fp32 row-major, 16-byte aligned; B (C, C + K) = [R^T | M] row-major; bias (C + K) =
+ *   [q | c]; beta; s = exp(logit_scale).  out (n, K) = s * (x B + bias)[C:] / sqrt(|(x B + bias)[:C]|^2 + beta).  No
+ *   division guard: a zero h gives NaN as the reference's 0 / 0 does.  Products on the fp32 matrix cores (exact fma
+ *   chains); no atomics, two runs are bitwise equal.  Forward only: training composes the head in torch.
+ * ptv3_ppt_head_capable: C a multiple of 16 in [16, 128], K in [1, 256].  Anything else is refused with
+ *   ptv3_last_error set and nothing launched. */
+int ptv3_ppt_head_capable(int C, int K);
+int ptv3_ppt_head_fwd(const float* x, const float* B, const float* bias, float beta, float s, int64_t n, int C, int K,
+                      float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,12 @@ from pointcept.models.utils.sparse import SubMConv3d, _ParamCache
 from pointcept.models.utils.hip_layers import (Linear, LayerNorm, BatchNorm1d, GELU, DropPath, _no_training,
                                                 check_sync_batchnorm)
 from pointcept.models.modules import PointModule, PointSequential
+from pointcept.models.point_prompt_training.prompt_driven_normalization import PDNorm, resolve_norm
+
+
+# False: a PDNorm is never resolved to its active plain norm, so every wrapped norm takes the generic branches.  Exists
+# for tools/bench_ppt.py, which measures what the resolution is worth; nothing else clears it.
+RESOLVE_PDNORM = True
 
 
 class RPE(nn.Module):
@@ -244,18 +250,25 @@ class Block(PointModule):
             norm_layer(channels),
         )
 
-    def _fusable(self):
-        return (self.pre_norm and isinstance(self.cpe[2], LayerNorm) and isinstance(self.norm1[0], LayerNorm)
-                and isinstance(self.norm2[0], LayerNorm) and isinstance(self.cpe[0], SubMConv3d)
+    def _norms(self, point=None):
+        """(the CPE's last norm, norm1, norm2) as the fused paths read them: a non-adaptive PDNorm stands for the plain
+        norm of the point's condition (resolve_norm), so a prompt-driven tree keeps the fused kernels"""
+        return tuple(resolve_norm(m, point) for m in (self.cpe[-1], self.norm1[0], self.norm2[0]))
+
+    def _fusable(self, norms=None):
+        n0, n1, n2 = norms or self._norms()
+        return (self.pre_norm and isinstance(n0, LayerNorm) and isinstance(n1, LayerNorm)
+                and isinstance(n2, LayerNorm) and isinstance(self.cpe[0], SubMConv3d)
                 and isinstance(self.cpe[1], Linear))
 
-    def _rows_path(self, feat):
+    def _rows_path(self, feat, norms=None):
         """the executor's rule (csrc/engine.hip Run::rows_path): every linear of the block served by ptv3_rows_linear and
         enough rows for its grid of 64 | 128-row workgroups"""
         mlp = self.mlp[0]
         n, c = feat.shape
+        n0, n1, n2 = norms or self._norms()
         return (n >= ops.rows_linear_rows() and isinstance(mlp.act, nn.GELU) and self.attn.qkv.bias is not None
-                and self.cpe[-1].eps == self.norm1[0].eps == self.norm2[0].eps
+                and n0.eps == n1.eps == n2.eps
                 and all(ops.rows_linear_capable(c, co, feat.dtype, n) for co in (3 * c, c, mlp.fc1.out_features)))
 
     def _param_cache(self):
@@ -290,21 +303,22 @@ class Block(PointModule):
         return self._param_cache().get(("chain", dtype), [self.attn.qkv.weight, self.attn.proj.weight, mlp.fc1.weight,
                                                           mlp.fc2.weight], make)
 
-    def _eval_after_cpe(self, point: Point, x=None, slabs=None, conv_bias=None):
+    def _eval_after_cpe(self, point: Point, x=None, slabs=None, conv_bias=None, norms=None):
         """Eval, from the CPE's linear part to the end of the block.  The rows in front of the CPE's last LayerNorm come
         as `x` (N, C), or still as the split-K `slabs` of ops.conv_slabs with their `conv_bias`.  The branches are the
         executor's (csrc/engine.hip): the fused halves where ptv3_block_fusable serves the shape (conv -> block_head ->
         window attention -> block_tail: 4 launches), else residual adds and norms folded into the epilogues of
         ptv3_layernorm[_slabs] + GEMMs, or of ptv3_rows_linear where _rows_path says so (9 launches)."""
-        mlp, qkv_lin, norm2 = self.mlp[0], self.attn.qkv, self.norm2[0]
+        mlp, qkv_lin = self.mlp[0], self.attn.qkv
+        norm0, norm1, norm2 = norms = norms or self._norms()
         shortcut = point.feat
         n, dt = shortcut.shape[0], shortcut.dtype
-        g0, b0 = self.cpe[-1].affine_f32()
-        g1, b1 = self.norm1[0].affine_f32()
+        g0, b0 = norm0.affine_f32()
+        g1, b1 = norm1.affine_f32()
         g2, b2 = norm2.affine_f32()
-        eps = self.cpe[-1].eps
+        eps = norm0.eps
         if (ops.block_fusable(self.channels, mlp.fc1.out_features, dt, n) and isinstance(mlp.act, nn.GELU)
-                and eps == self.norm1[0].eps == norm2.eps and qkv_lin.bias is not None):   # the head reads bqkv
+                and eps == norm1.eps == norm2.eps and qkv_lin.bias is not None):   # the head reads bqkv
             wqkv, wproj, w1, w2 = self.chain_weights(dt)
             slab, splits = slabs if slabs is not None else (None, 0)
             f1, qkv = ops.block_head(x, slab, splits, conv_bias, shortcut, g0, b0, g1, b1, wqkv, qkv_lin.bias_f32(), eps)
@@ -312,7 +326,7 @@ class Block(PointModule):
             feat = ops.block_tail(x, f1, wproj, self.attn.proj.bias_f32(), g2, b2, w1, mlp.fc1.bias_f32(), w2,
                                   mlp.fc2.bias_f32(), eps)
         else:
-            rows = self._rows_path(shortcut)
+            rows = self._rows_path(shortcut, norms)
             if slabs is not None:   # deep levels: the conv splits over K; the LayerNorm kernel sums the slabs
                 feat, x = ops.layernorm_slabs(slabs[0], slabs[1], n, self.channels, conv_bias, dt, g0, b0, eps,
                                               res=shortcut, gamma2=g1, beta2=b1)
@@ -336,13 +350,14 @@ class Block(PointModule):
         point.sparse_conv_feat = point.sparse_conv_feat.replace_feature(feat)
         return point
 
-    def _train_fusable(self):
+    def _train_fusable(self, norms=None):
         mlp = self.mlp[0]
+        n0, n1, n2 = norms = norms or self._norms()
         drops = [self.attn.proj_drop, mlp.drop] + ([self.attn.attn_drop] if isinstance(self.attn.attn_drop, nn.Dropout) else [])
         flash_drop = (not isinstance(self.attn.attn_drop, nn.Dropout)) and float(self.attn.attn_drop) > 0.0
-        return (self._fusable() and isinstance(mlp.act, nn.GELU) and not self.attn.enable_rpe and not flash_drop
+        return (self._fusable(norms) and isinstance(mlp.act, nn.GELU) and not self.attn.enable_rpe and not flash_drop
                 and all(d.p == 0.0 for d in drops) and self.cpe[0].bias is not None
-                and self.cpe[2].eps == self.norm1[0].eps == self.norm2[0].eps
+                and n0.eps == n1.eps == n2.eps
                 and isinstance(self.drop_path[0], (DropPath, nn.Identity)))
 
     def _drop_draw(self, point):
@@ -362,43 +377,45 @@ class Block(PointModule):
         pool[1] += 1
         return row, 1.0 - dp.drop_prob
 
-    def _forward_train(self, point: Point):
+    def _forward_train(self, point: Point, norms=None):
         """Training: the whole block as ONE taped Function (ptv3_hip.autograd.BlockFn) - same kernels and statement
         order as _forward_generic, without a trip through the autograd engine per layer."""
         spt = point.sparse_conv_feat
         feat = point.feat
         conv_feat = None if spt.features is feat else spt.features
         mlp = self.mlp[0]
+        n0, n1, n2 = norms or self._norms()
         K = self.attn.resolve_patch_size(point)
         wo, wi = self.attn.window_maps(point)
-        params = (self.cpe[0].weight, self.cpe[0].bias, self.cpe[1].weight, self.cpe[1].bias, self.cpe[2].weight,
-                  self.cpe[2].bias, self.norm1[0].weight, self.norm1[0].bias, self.attn.qkv.weight, self.attn.qkv.bias,
-                  self.attn.proj.weight, self.attn.proj.bias, self.norm2[0].weight, self.norm2[0].bias,
+        params = (self.cpe[0].weight, self.cpe[0].bias, self.cpe[1].weight, self.cpe[1].bias, n0.weight,
+                  n0.bias, n1.weight, n1.bias, self.attn.qkv.weight, self.attn.qkv.bias,
+                  self.attn.proj.weight, self.attn.proj.bias, n2.weight, n2.bias,
                   mlp.fc1.weight, mlp.fc1.bias, mlp.fc2.weight, mlp.fc2.bias)
         # the two DropPath draws in the reference's order: attention branch, then MLP branch
         mask1 = self._drop_draw(point)
         mask2 = self._drop_draw(point)
         out = A.block(feat, conv_feat, params, spt.neighbors(3, self.cpe[0].indice_key), spt.row_order, wo, wi,
-                      self.attn.num_heads, K, self.attn.scale, mask1, mask2, self.cpe[2].eps,
+                      self.attn.num_heads, K, self.attn.scale, mask1, mask2, n0.eps,
                       self.attn.window_cu(point))
         point.feat = out
         point.sparse_conv_feat = spt.replace_feature(out)
         return point
 
     def forward(self, point: Point):
-        if self.training and self._train_fusable() and point.feat.shape[1] % ops.k_granule(point.feat.dtype) == 0 \
+        norms = self._norms(point) if RESOLVE_PDNORM else None
+        if self.training and self._train_fusable(norms) and point.feat.shape[1] % ops.k_granule(point.feat.dtype) == 0 \
                 and self.attn.qkv.bias is not None:
-            return self._forward_train(point)
-        if self.training or not self._fusable():
+            return self._forward_train(point, norms)
+        if self.training or not self._fusable(norms):
             return self._forward_generic(point)
         spt = point.sparse_conv_feat                         # xCPE conv reads the sparse tensor's features
         wf, bf = self.folded_cpe(spt.features.dtype)
         nbr = spt.neighbors(3, self.cpe[0].indice_key)
         slabs = ops.conv_slabs(spt.features, wf, nbr, 27, spt.row_order)
         if slabs is not None:
-            return self._eval_after_cpe(point, slabs=slabs, conv_bias=bf)
+            return self._eval_after_cpe(point, slabs=slabs, conv_bias=bf, norms=norms)
         x = ops.gemm(spt.features, wf, bias=bf, nbr=nbr, kvol=27, row_order=spt.row_order)
-        return self._eval_after_cpe(point, x=x)
+        return self._eval_after_cpe(point, x=x, norms=norms)
 
     def _forward_generic(self, point: Point):
         """The reference's statement order (:318-338) on the unfused layer ops."""
@@ -521,7 +538,9 @@ class SerializedPooling(PointModule):
         else:
             perm = None
         # folded BN + activation ride on the segmented max when they are the standard eval layers
-        bn = self.norm[0] if self.norm is not None and len(self.norm) == 1 and isinstance(self.norm[0], BatchNorm1d) else None
+        bn = resolve_norm(self.norm[0], point if RESOLVE_PDNORM else None) if self.norm is not None and len(self.norm) == 1 \
+            else None
+        bn = bn if isinstance(bn, BatchNorm1d) else None
         act_id = ops.ACT_NONE
         fuse = (self.norm is None or bn is not None) and (self.act is None or isinstance(self.act[0], nn.GELU))
         fuse = fuse and not self.training   # training: BN needs the batch statistics of the pooled rows
@@ -583,9 +602,10 @@ class SerializedUnpooling(PointModule):
         self.traceable = traceable
 
     @staticmethod
-    def _epilogue(seq):
-        """(bn_scale, bn_shift, act) when `seq` is Linear [+ eval BatchNorm1d] [+ GELU], else None."""
-        mods = list(seq._modules.values())
+    def _epilogue(seq, point=None):
+        """(bn_scale, bn_shift, act) when `seq` is Linear [+ eval BatchNorm1d] [+ GELU], else None.  A non-adaptive PDNorm
+        counts as the BatchNorm1d of the point's condition."""
+        mods = [resolve_norm(m, point) for m in seq._modules.values()]
         if not isinstance(mods[0], Linear):
             return None
         scale = shift = None
@@ -607,7 +627,8 @@ class SerializedUnpooling(PointModule):
         parent = point.pop("pooling_parent")
         inverse = point.pop("pooling_inverse")
         segments = point.pop("_pool_segments", None)
-        e1, e2 = (None, None) if self.training else (self._epilogue(self.proj), self._epilogue(self.proj_skip))
+        at = point if RESOLVE_PDNORM else None
+        e1, e2 = (None, None) if self.training else (self._epilogue(self.proj, at), self._epilogue(self.proj_skip, at))
         if e1 is not None and e2 is not None:
             # two GEMMs: up-branch, then skip-branch whose epilogue gathers the up-branch rows by cluster id
             up = self.proj[0](point.feat, bn_scale=e1[0], bn_shift=e1[1], act=e1[2])
@@ -645,7 +666,7 @@ class Embedding(PointModule):
 
     def forward(self, point: Point):
         mods = self.stem._modules
-        bn, act = mods.get("norm"), mods.get("act")
+        bn, act = resolve_norm(mods.get("norm"), point if RESOLVE_PDNORM else None), mods.get("act")
         if not self.training and (bn is None or isinstance(bn, BatchNorm1d)) and (act is None or isinstance(act, nn.GELU)):
             scale, shift = bn.folded() if bn is not None else (None, None)
             sp = mods["conv"](point.sparse_conv_feat, bn_scale=scale, bn_shift=shift,
@@ -730,11 +751,20 @@ class PointTransformerV3(PointModule):
         assert self.enc_mode or self.num_stages == len(dec_num_head) + 1
         assert self.enc_mode or self.num_stages == len(dec_patch_size) + 1
 
-        if pdnorm_bn or pdnorm_ln:
-            raise NotImplementedError("PDNorm (pdnorm_bn / pdnorm_ln) is off in every target config and is not "
-                                      "part of the MI355X path (SURVEY.md section 2a row 10)")
-        bn_layer = partial(BatchNorm1d, eps=1e-3, momentum=0.01)
-        ln_layer = LayerNorm
+        # norm layers (:570-591): PDNorm over the library's own norms; context_channels stays at PDNorm's 256
+        if (pdnorm_bn or pdnorm_ln) and not pdnorm_decouple:
+            raise ValueError("PT-v3m1: pdnorm_decouple=False cannot run in the reference (PDNorm keeps the norm's "
+                             "constructor instead of a norm and calls it on the features)")
+        if pdnorm_bn:
+            bn_layer = partial(PDNorm, norm_layer=partial(BatchNorm1d, eps=1e-3, momentum=0.01, affine=pdnorm_affine),
+                               conditions=pdnorm_conditions, decouple=pdnorm_decouple, adaptive=pdnorm_adaptive)
+        else:
+            bn_layer = partial(BatchNorm1d, eps=1e-3, momentum=0.01)
+        if pdnorm_ln:
+            ln_layer = partial(PDNorm, norm_layer=partial(LayerNorm, elementwise_affine=pdnorm_affine),
+                               conditions=pdnorm_conditions, decouple=pdnorm_decouple, adaptive=pdnorm_adaptive)
+        else:
+            ln_layer = LayerNorm
         act_layer = GELU
 
         self.embedding = Embedding(in_channels=in_channels, embed_channels=enc_channels[0], norm_layer=bn_layer,

@@ -226,3 +226,30 @@ CAC_PTV2_SCANNET200_CFG = dict(
     criteria=_CAC_CRITERIA, num_classes=200, backbone_out_channels=48, cos_temp=15, main_weight=1, pre_weight=1,
     pre_self_weight=1, kl_weight=1, conf_thresh=0, detach_pre_logits=True,
 )
+
+# Point Prompt Training: the `model` dict of configs/scannet/semseg-pt-v3m1-1-ppt-extreme.py:30-92 (class_name and
+# valid_index are the class defaults there and here), and a tiny PPT-v1m2 (decoupled heads) on PT-v3m1
+PPT_PTV3_SCANNET_CFG = dict(
+    type="PPT-v1m1",
+    backbone=dict(
+        type="PT-v3m1", in_channels=6, order=("z", "z-trans", "hilbert", "hilbert-trans"), stride=(2, 2, 2, 2),
+        enc_depths=(3, 3, 3, 6, 3), enc_channels=(48, 96, 192, 384, 512), enc_num_head=(3, 6, 12, 24, 32),
+        enc_patch_size=(1024, 1024, 1024, 1024, 1024), dec_depths=(3, 3, 3, 3), dec_channels=(64, 96, 192, 384),
+        dec_num_head=(4, 6, 12, 24), dec_patch_size=(1024, 1024, 1024, 1024), mlp_ratio=4, qkv_bias=True,
+        qk_scale=None, attn_drop=0.0, proj_drop=0.0, drop_path=0.3, shuffle_orders=True, pre_norm=True,
+        enable_rpe=False, enable_flash=True, upcast_attention=False, upcast_softmax=False, enc_mode=False,
+        pdnorm_bn=True, pdnorm_ln=True, pdnorm_decouple=True, pdnorm_adaptive=False, pdnorm_affine=True,
+        pdnorm_conditions=("ScanNet", "S3DIS", "Structured3D")),
+    criteria=_CAC_CRITERIA, backbone_out_channels=64, context_channels=256,
+    conditions=("Structured3D", "ScanNet", "S3DIS"), template="[x]", clip_model="ViT-B/16", backbone_mode=False,
+)
+PPT_V1M2_TINY_CFG = dict(
+    type="PPT-v1m2",
+    backbone=dict(
+        type="PT-v3m1", in_channels=4, order=("z", "z-trans"), stride=(2, 2), enc_depths=(1, 1, 1),
+        enc_channels=(16, 32, 64), enc_num_head=(1, 2, 4), enc_patch_size=(16, 16, 16), dec_depths=(1, 1),
+        dec_channels=(16, 32), dec_num_head=(1, 2), dec_patch_size=(16, 16), drop_path=0.0, enable_flash=False,
+        pdnorm_bn=True, pdnorm_ln=True, pdnorm_conditions=("A", "B", "C")),
+    criteria=[dict(type="CrossEntropyLoss", loss_weight=1.0, ignore_index=-1)], backbone_out_channels=16,
+    context_channels=256, conditions=("A", "B", "C"), num_classes=(5, 7, 3), backbone_mode=False,
+)

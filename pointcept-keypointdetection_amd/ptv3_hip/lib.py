@@ -246,6 +246,8 @@ SIGNATURES = {
     "ptv3_cac_distill_workspace_bytes": (c_size_t, [c_int64, c_int]),
     "ptv3_cac_distill_fwd": (c_int, [P, P, P, c_int64, c_int, P, P, P, P, c_size_t, P]),
     "ptv3_cac_distill_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P, P]),
+    "ptv3_ppt_head_capable": (c_int, [c_int, c_int]),
+    "ptv3_ppt_head_fwd": (c_int, [P, P, P, c_float, c_float, c_int64, c_int, c_int, P, P]),
 }
 
 

@@ -1687,6 +1687,64 @@ def cac_distill_bwd(dloss, pred, soft, labels, coef):
 
 
 # ---------------------------------------------------------------------------------------------
+# language-guided head of Point Prompt Training (csrc/ppt_head.hip)
+# ---------------------------------------------------------------------------------------------
+def ppt_head_capable(c, k):
+    """(C channels, K valid classes) ptv3_ppt_head_fwd covers: C a multiple of 16 in [16, 128], 1 <= K <= 256."""
+    return bool(lib.ptv3_ppt_head_capable(int(c), int(k)))
+
+
+def ppt_head_qr(W, b=None):
+    """The part of the collapse that depends on proj_head alone, float64 on the host: W (D, C) = Q R (thin) ->
+    (R (C, C), q = Q^T b (C), beta = |b - Q q|^2 as a float).  With D < C the factor has D rows only; R and q are
+    filled up with zeros to C, which changes no sum of squares."""
+    W = W.detach().double().cpu()
+    d, c = W.shape
+    b = torch.zeros(d, dtype=torch.float64) if b is None else b.detach().double().cpu()
+    Q, R = torch.linalg.qr(W, mode="reduced")
+    q = Q.t() @ b
+    rest = b - Q @ q
+    if d < c:
+        R = torch.cat([R, torch.zeros(c - d, c, dtype=torch.float64)])
+        q = torch.cat([q, torch.zeros(c - d, dtype=torch.float64)])
+    return R, q, float(rest @ rest)
+
+
+def ppt_head_collapse(W, b, E_v, logit_scale, qr=None, dtype=torch.float32):
+    """proj_head (W (D, C), b (D) or None), the K valid class embeddings E_v (K, D) and logit_scale -> the operands of
+    the collapsed head (include/ptv3_hip.h): (B (C, C + K) = [R^T | M], bias (C + K) = [q | c], beta, s), computed in
+    float64 on the host and rounded once to `dtype`, on W's device; beta and s = exp(logit_scale) are floats.
+    seg_logits = s * (x B + bias)[:, C:] / sqrt(|(x B + bias)[:, :C]|^2 + beta).  `qr`: a ppt_head_qr(W, b) result
+    to reuse (it does not depend on the condition)."""
+    R, q, beta = ppt_head_qr(W, b) if qr is None else qr
+    W64 = W.detach().double().cpu()
+    E64 = E_v.detach().double().cpu()
+    b64 = torch.zeros(W64.shape[0], dtype=torch.float64) if b is None else b.detach().double().cpu()
+    M = W64.t() @ E64.t()
+    c = E64 @ b64
+    B = torch.cat([R.t(), M], 1).to(dtype).contiguous().to(W.device)
+    bias = torch.cat([q, c]).to(dtype).contiguous().to(W.device)
+    s = float(torch.as_tensor(logit_scale).detach().double().exp())
+    return B, bias, beta, s
+
+
+def ppt_head(x, B, bias, beta, s):
+    """x (N, C) fp32 and the operands of ppt_head_collapse -> seg_logits (N, K) fp32, one launch."""
+    _chk(x, "ppt_head: x", torch.float32, 2)
+    _chk(B, "ppt_head: B", torch.float32, 2)
+    _chk(bias, "ppt_head: bias", torch.float32, 1)
+    n, c = x.shape
+    k = B.shape[1] - c
+    if B.shape[0] != c or bias.shape[0] != B.shape[1]:
+        raise RuntimeError(f"ppt_head: x {tuple(x.shape)} / B {tuple(B.shape)} / bias {tuple(bias.shape)}: expected "
+                           "(N, C), (C, C + K), (C + K)")
+    out = torch.empty((n, max(k, 0)), dtype=torch.float32, device=x.device)
+    lib.check(lib.ptv3_ppt_head_fwd(_p(x), _p(B), _p(bias), float(beta), float(s), n, c, k, _p(out), _stream()),
+              "ptv3_ppt_head_fwd")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # pointops
 # ---------------------------------------------------------------------------------------------
 def knn_query(nsample, xyz, offset, new_xyz, new_offset):
