@@ -231,12 +231,23 @@ window_attn_kernel(const T* __restrict__ qkv, const int32_t* __restrict__ win_or
 // ------------------------------------------------------------------------------------------------
 // Resident-window variant: the K and V of the whole (window, head) are staged into LDS ONCE
 // (bf16, K=1024, head_dim 16: 40 KB + 33 KB), then every wave streams its 64 queries over all key
-// tiles with no further barrier.  Softmax rescale is lazy: the cross-lane max exchange and the O / l
-// rescale only run (wave-uniformly) when some row maximum grew by more than 2^8 since the last
-// rescale; exact (softmax is shift invariant), removes two lane exchanges per tile from the
-// dependency chain.  Used whenever the window fits LDS; the tiled kernel above is the fallback.
+// tiles with no further barrier.  The walk keeps no running maximum: the first key tile pins every
+// row's reference to its maximum there, the later tiles add exp2(score - reference) as it comes
+// (softmax is shift invariant; fp32 and bf16 keep their relative precision whatever the exponent).
+// After the walk every 16-query tile checks that its sums stayed in range; one that did not - logits
+// that rise by more than 64 log2 units along the keys - is walked again with the lazy rescale: the
+// cross-lane max exchange and the O / l rescale run (wave-uniformly) when some row maximum grew by
+// more than 2^8 since the last rescale.  Used whenever the window fits LDS; the tiled kernel above
+// is the fallback.
 // ------------------------------------------------------------------------------------------------
-constexpr float WA_RESCALE_THR = 8.0f;  // log2 units: probabilities stay <= 256 between rescales
+constexpr float WA_RESCALE_THR = 8.0f;  // log2 units: probabilities stay <= 256 between rescales (exact walk)
+// Deferred walk: a query tile passes when every row sum l = sum_keys p, p = exp2(score - reference) >= 0, is below
+// 2^64.  Then every single p is below 2^64 as well (so none was rounded to infinity, in fp32 or in bf16, and l, 1 / l
+// and log2 l are ordinary numbers), and |o| <= sum p |v| < 2^64 max |v| is finite for |v| < 2^63, a factor 2 of room
+// for the rounding of the sum below the fp32 limit 2^128.  Larger v are caught by the test of o itself.  The bound is
+// compared on the bits of l: exponent field >= 127 + 64, which also holds for infinity and NaN.
+constexpr unsigned WA_DEFER_BOUND_BITS = (127u + 64u) << 23;
+enum { WA_PIN = 0, WA_DEFER = 1, WA_EXACT = 2 };
 
 __device__ __forceinline__ float lanes_max_groups(float x) {
   // all-reduce max over the 4 lane groups g = lane >> 4 that share one query (lanes l, l^16, l^32, l^48);
@@ -410,8 +421,16 @@ window_attn_full_kernel(const T* __restrict__ qkv, const int32_t* __restrict__ w
   V4 ones = RowSum<T>::ones();
   asm volatile("" : "+v"(ones));
 
-  auto tile_body = [&](const int tile, auto mask_tag) {
+  // One 64-key tile against the wave's query tiles, in one of three modes:
+  //   WA_PIN    first tile of the deferred walk: the reference of every row becomes its maximum in this tile
+  //   WA_DEFER  later tiles of the deferred walk: no maximum, no compare, no branch - the score product starts from
+  //             negm, then exp2, pack, row sum and P V.  Whether the unscaled sums stayed in range is checked once
+  //             per query tile after the walk (below)
+  //   WA_EXACT  the lazy-rescale body, for the query tiles that have to be walked again
+  // `redo` (wave-uniform, WA_EXACT only): the query tiles of the wave that are walked
+  auto tile_body = [&](const int tile, auto mask_tag, auto mode_tag, const unsigned redo) {
     constexpr bool MASK = decltype(mask_tag)::value;
+    constexpr int MODE = decltype(mode_tag)::value;
     const int key0 = tile * WA_KT;
     V4 kf[4][ND], vf[ND][4];
 #pragma unroll
@@ -423,6 +442,7 @@ window_attn_full_kernel(const T* __restrict__ qkv, const int32_t* __restrict__ w
       }
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
+      if (MODE == WA_EXACT && !((redo >> t) & 1u)) continue;
       f32x4 s[4];  // score - reference max, log2 domain
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) {
@@ -465,29 +485,31 @@ window_attn_full_kernel(const T* __restrict__ qkv, const int32_t* __restrict__ w
           for (int r = 0; r < 4; ++r)
             if (key0 + 16 * kt + 4 * g + r >= K) s[kt][r] = -INFINITY;
       }
-      // 16 values -> 8 x v_max3_f32
-      float mx = max3_raw(s[0][0], s[0][1], s[0][2]);
-      mx = max3_raw(mx, s[0][3], s[1][0]);
-      mx = max3_raw(mx, s[1][1], s[1][2]);
-      mx = max3_raw(mx, s[1][3], s[2][0]);
-      mx = max3_raw(mx, s[2][1], s[2][2]);
-      mx = max3_raw(mx, s[2][3], s[3][0]);
-      mx = max3_raw(mx, s[3][1], s[3][2]);
-      mx = fmaxf(mx, s[3][3]);
-      // Lazy rescale (wave-uniform): the first tile pins the reference to its row maximum; afterwards the
-      // exchange + rescale only run when some row maximum outgrew the reference by more than 2^THR.
-      if (__builtin_expect(tile == 0 || __any(mx > WA_RESCALE_THR), 0)) {
-        float d = lanes_max_groups(mx);      // new max - old reference (same for the 4 lanes of a query)
-        if (tile > 0) d = fmaxf(d, 0.f);     // the reference never moves down after the first tile
-        if (tile > 0) {
-          const float alpha = __builtin_amdgcn_exp2f(-d);
-          lacc[t] *= alpha;
+      if constexpr (MODE != WA_DEFER) {
+        // 16 values -> 8 x v_max3_f32
+        float mx = max3_raw(s[0][0], s[0][1], s[0][2]);
+        mx = max3_raw(mx, s[0][3], s[1][0]);
+        mx = max3_raw(mx, s[1][1], s[1][2]);
+        mx = max3_raw(mx, s[1][3], s[2][0]);
+        mx = max3_raw(mx, s[2][1], s[2][2]);
+        mx = max3_raw(mx, s[2][3], s[3][0]);
+        mx = max3_raw(mx, s[3][1], s[3][2]);
+        mx = fmaxf(mx, s[3][3]);
+        // The first tile pins the reference to its row maximum.  WA_EXACT, lazy rescale (wave-uniform): afterwards
+        // the exchange + rescale only run when some row maximum outgrew the reference by more than 2^THR.
+        if (MODE == WA_PIN || __builtin_expect(tile == 0 || __any(mx > WA_RESCALE_THR), 0)) {
+          float d = lanes_max_groups(mx);      // new max - old reference (same for the 4 lanes of a query)
+          if (MODE == WA_EXACT && tile > 0) {
+            d = fmaxf(d, 0.f);                 // the reference never moves down after the first tile
+            const float alpha = __builtin_amdgcn_exp2f(-d);
+            lacc[t] *= alpha;
 #pragma unroll
-          for (int c = 0; c < ND; ++c) o[t][c] *= alpha;
+            for (int c = 0; c < ND; ++c) o[t][c] *= alpha;
+          }
+          negm[t] -= d;
+#pragma unroll
+          for (int kt = 0; kt < 4; ++kt) s[kt] -= d;
         }
-        negm[t] -= d;
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt) s[kt] -= d;
       }
       float ps = 0.f;
       V4 pf[4];
@@ -517,8 +539,43 @@ window_attn_full_kernel(const T* __restrict__ qkv, const int32_t* __restrict__ w
   };
 
   const int full_tiles = K / WA_KT;
-  for (int tile = 0; tile < full_tiles; ++tile) tile_body(tile, std::false_type{});
-  if (full_tiles * WA_KT < K) tile_body(full_tiles, std::true_type{});
+  const bool tail = full_tiles * WA_KT < K;
+  using Pin = std::integral_constant<int, WA_PIN>;
+  using Defer = std::integral_constant<int, WA_DEFER>;
+  using Exact = std::integral_constant<int, WA_EXACT>;
+  // ---- deferred walk.  The pin tile always takes the masked form (on a full tile the mask changes nothing): one
+  // instantiation less, off the steady-state loop.
+  tile_body(0, std::true_type{}, Pin{}, 0u);
+  for (int tile = 1; tile < full_tiles; ++tile) tile_body(tile, std::false_type{}, Defer{}, 0u);
+  if (tail && full_tiles > 0) tile_body(full_tiles, std::true_type{}, Defer{}, 0u);
+
+  // ---- did the unscaled sums stay in range?  Decided per 16-query tile (its 64 lanes are this wave's), never per
+  // wave: a tile's bits must not depend on the tiles it shares a wave with.  A tile is walked again, exactly, when
+  // its row sum is NaN or at or above 2^64 (WA_DEFER_BOUND_BITS), or a component of o is not finite, in any lane.
+  unsigned redo = 0;
+#pragma unroll
+  for (int t = 0; t < QT; ++t) {
+    const float lsum = SUM_MFMA ? lacc[t][0] : lanes_sum_groups(lacc[t][0]);
+    // on the bits: this file is compiled without NaNs in its floating-point model
+    bool bad = (__float_as_uint(lsum) & 0x7fffffffu) >= WA_DEFER_BOUND_BITS;
+#pragma unroll
+    for (int c = 0; c < ND; ++c)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) bad |= (__float_as_uint(o[t][c][r]) & 0x7f800000u) == 0x7f800000u;
+    if (__any(bad)) redo |= 1u << t;
+  }
+  if (__builtin_expect(redo != 0, 0)) {
+#pragma unroll
+    for (int t = 0; t < QT; ++t) {
+      if (!((redo >> t) & 1u)) continue;
+      negm[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      lacc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < ND; ++c) o[t][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    for (int tile = 0; tile < full_tiles; ++tile) tile_body(tile, std::false_type{}, Exact{}, redo);
+    if (tail) tile_body(full_tiles, std::true_type{}, Exact{}, redo);
+  }
 
 #pragma unroll
   for (int t = 0; t < QT; ++t) {
