@@ -1285,6 +1285,45 @@ int ptv3_ppt_head_capable(int C, int K);
 int ptv3_ppt_head_fwd(const float* x, const float* B, const float* bias, float beta, float s, int64_t n, int C, int K,
                       float* out, void* stream);
 
+/* Self-distillation loss of "Sonata-v1m1", pointcept/models/sonata/sonata_v1m1_base.py:267-291 and :443-454
+ * (csrc/sonata_loss.hip).  x (nt, K) teacher logits and s (ns, K) student logits, row-major, fp32
+ * (PTV3_F32) or bf16 (PTV3_BF16) each; idx_t / idx_s (M) the matched rows, int64 or int32 (`*_i32` != 0); idx_t may
+ * repeat, idx_s is strictly increasing; an index outside its matrix is clamped to it.  With E = exp(x[idx_t] / T) the
+ * reference's Sinkhorn-Knopp assignment (three row / column rounds) is target[m, k] = E[m, k] u[k] / d[m],
+ * d[m] = sum_k E[m, k] u[k]; u is the result of three sweeps:
+ *   u1 = 1 / (K A1), A1[k] = sum_m E[m, k];  u_{i+1} = 1 / (K A_{i+1}), A_{i+1}[k] = sum_m E[m, k] / (n d_i[m]),
+ * n the number of pairs of all ranks.  exp is taken without a shift as the reference does: the logits are cosines and
+ * T >= 0.04, so |x / T| <= 25; 1 / T and 1 / tau must be finite and positive.  For an even K the kernels access pairs of
+ * columns (8 bytes in fp32, 4 in bf16) when x, s, u and ds start on such a boundary, and single columns otherwise: no
+ * alignment is required, an aligned base is faster.  No atomics, two runs are bitwise equal,
+ * nothing is read back by the host.  M = 0 is the caller's case (loss 0, nothing launched).
+ * ptv3_sonata_capable: 2 <= K <= 4096.
+ * ptv3_sonata_sk_pass: one sweep.  u == NULL: A[k] = sum_m E[m, k].  Otherwise A[k] = sum_m E[m, k] / (n_total d[m])
+ *   with d from u in the same sweep; a row is read once.  A (K) is this rank's sum; u_next (K, may be NULL) =
+ *   1 / (K A), for a caller that has nothing to reduce across ranks.  Workgroups take 64 pairs and store their K sums
+ *   in the workspace (ptv3_sonata_sk_workspace_bytes(M, K)); the chunks are added in increasing order in float64.
+ * ptv3_sonata_ce_fwd: loss_m = -sum_k target[m, k] (s[idx_s[m], k] / tau - lse[m]); the pairs of a scene of offset_s
+ *   (nb cumulative ends of the student's scenes) are averaged, then the scenes 0 .. B - 1, B = 1 + the scene of the last
+ *   pair: an empty scene below B counts with 0, the empty scenes behind it do not count (segment_coo(reduce="mean")
+ *   with dim_size = index.max() + 1).  loss (1), d (M), lse (M), gscale (nb) = 1 / (count_b B) or 0, all fp32.
+ *   workspace: ptv3_sonata_ce_workspace_bytes(M).
+ * ptv3_sonata_ce_bwd: ds (ns, K) in the dtype of s: dloss[0] gscale[b] (softmax(s / tau) sum_k target - target) / tau in
+ *   a matched row, exact zeros elsewhere; the target is recomputed from x, u and d.  The teacher gets no gradient. */
+int ptv3_sonata_capable(int K);
+size_t ptv3_sonata_sk_workspace_bytes(int64_t M, int K);
+int ptv3_sonata_sk_pass(const void* x, int x_dtype, const void* idx_t, int idx_i32, int64_t nt, int64_t M, int K,
+                        double inv_temp, const float* u, double n_total, float* A, float* u_next, void* workspace,
+                        size_t workspace_bytes, void* stream);
+size_t ptv3_sonata_ce_workspace_bytes(int64_t M);
+int ptv3_sonata_ce_fwd(const void* x, int x_dtype, const void* idx_t, int idx_t_i32, int64_t nt, const void* s,
+                       int s_dtype, const void* idx_s, int idx_s_i32, int64_t ns, int64_t M, int K, double inv_temp,
+                       double inv_tau, const float* u, const int64_t* offset_s, int nb, float* loss, float* d, float* lse,
+                       float* gscale, void* workspace, size_t workspace_bytes, void* stream);
+int ptv3_sonata_ce_bwd(const float* dloss, const void* x, int x_dtype, const void* idx_t, int idx_t_i32, int64_t nt,
+                       const void* s, int s_dtype, const void* idx_s, int idx_s_i32, int64_t ns, int64_t M, int K,
+                       double inv_temp, double inv_tau, const float* u, const float* d, const float* lse,
+                       const int64_t* offset_s, int nb, const float* gscale, void* ds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

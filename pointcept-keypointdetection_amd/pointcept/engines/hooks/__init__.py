@@ -28,3 +28,4 @@ class HookBase:
 # the evaluator hooks register themselves with HOOKS on import, as in the reference (engines/hooks/__init__.py:7-8)
 from .keypoint_evaluator import KeypointEvaluator  # noqa: E402,F401
 from .offset_keypoint_evaluator import OffsetKeypointEvaluator  # noqa: E402,F401
+from .default import ModelHook  # noqa: E402,F401

@@ -134,9 +134,13 @@ class GridPooling(PointModule):
                 point_dict[key_] = point[key_]
         if "grid_size" in point.keys():
             point_dict["grid_size"] = point.grid_size * self.stride
-        for key_ in ("origin_coord", "color"):
-            if key_ in point.keys():
-                raise NotImplementedError(f"GridPooling on the HIP path: mean-pooled '{key_}' (pre-training extras)")
+        if "origin_coord" in point.keys():
+            # the mean of the coordinates before the view's augmentation (:432-435): Sonata matches its views on it;
+            # the geometry half of the pooling kernel, so the same means as `coord`
+            point_dict["origin_coord"] = ops.pool_geometry(
+                point.origin_coord.float().contiguous(), gc, batch, key.view(1, -1), order, seg_start, n_out, shift)[0]
+        if "color" in point.keys():
+            raise NotImplementedError("GridPooling on the HIP path: mean-pooled 'color' (pre-training extra)")
         if self.traceable:
             point_dict["pooling_inverse"] = cluster
             point_dict["pooling_parent"] = point

@@ -581,6 +581,56 @@ def cac_distill(pred, soft, labels):
     return CacDistillFn.apply(pred, soft.detach(), labels)
 
 
+class SonataCeFn(Function):
+    """Cross entropy of Sonata's self-distillation against the Sinkhorn-Knopp target E u / d (ops.sonata_ce): the
+    gradient goes to the student logits alone.  Saved besides the inputs: d and lse per pair and the per-scene factor;
+    the target and the log-softmax are recomputed by the backward launch."""
+
+    @staticmethod
+    def forward(ctx, s, x, idx_t, idx_s, offset_s, u, inv_temp, inv_tau):
+        s, x, idx_t, idx_s = s.contiguous(), x.contiguous(), idx_t.contiguous(), idx_s.contiguous()
+        off = ops._scene_offset(offset_s.contiguous(), "offset_s")
+        loss, d, lse, gscale = ops.sonata_ce(x, idx_t, inv_temp, u, s, idx_s, inv_tau, off)
+        ctx.save_for_backward(s, x, idx_t, idx_s, off, u, d, lse, gscale)
+        ctx.scales = (inv_temp, inv_tau)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        s, x, idx_t, idx_s, off, u, d, lse, gscale = ctx.saved_tensors
+        ds = ops.sonata_ce_bwd(dloss.float().contiguous().view(1), x, idx_t, ctx.scales[0], u, s, idx_s, ctx.scales[1],
+                               off, d, lse, gscale)
+        return ds, None, None, None, None, None, None, None
+
+
+def sonata_scaling(x, idx_t, inv_temp, n_total=None, all_reduce=None):
+    """u (K) fp32 of the Sinkhorn-Knopp assignment of x[idx_t] / T: three sweeps (ops.sonata_sk_pass).  One rank: the
+    kernel forms the next u itself.  Several: all_reduce(A) sums the K partial sums in place before u = 1 / (K A), and
+    n_total counts the pairs of all ranks."""
+    x, idx_t = x.detach().contiguous(), idx_t.contiguous()
+    k = x.shape[1]
+    n = idx_t.shape[0] if n_total is None else n_total
+    u = None
+    for _ in range(3):
+        a, u_next = ops.sonata_sk_pass(x, idx_t, inv_temp, u, n, with_u=all_reduce is None)
+        if all_reduce is not None:
+            all_reduce(a)
+            u_next = 1.0 / (k * a)
+        u = u_next
+    return u
+
+
+def sonata_loss(s, x, idx_t, idx_s, offset_s, temp, student_temp, n_total=None, all_reduce=None):
+    """-> loss, 0-d fp32 with grad to s: the mean over scenes of the per-scene mean of
+    -sum_k sinkhorn_knopp(x[idx_t], temp)[m, k] log_softmax(s[idx_s[m]] / student_temp)[k]."""
+    if idx_t.shape[0] == 0 and all_reduce is None:
+        return s.sum() * 0.0
+    u = sonata_scaling(x, idx_t, 1.0 / temp, n_total, all_reduce)
+    if idx_t.shape[0] == 0:
+        return s.sum() * 0.0
+    return SonataCeFn.apply(s, x.detach(), idx_t, idx_s, offset_s, u, 1.0 / temp, 1.0 / student_temp)
+
+
 def linear(x, weight, bias=None):
     return LinearFn.apply(x, weight, bias)
 

@@ -253,3 +253,33 @@ PPT_V1M2_TINY_CFG = dict(
     criteria=[dict(type="CrossEntropyLoss", loss_weight=1.0, ignore_index=-1)], backbone_out_channels=16,
     context_channels=256, conditions=("A", "B", "C"), num_classes=(5, 7, 3), backbone_mode=False,
 )
+
+# Sonata pretraining: the `model` dict of configs/sonata/pretrain-sonata-v1m1-0-base.py:21-79, and a tiny one (three
+# stages, up-cast back to the input level, 100 prototypes; no order shuffle, drop path or jitter, so that the patch
+# permutation is the only random draw of a step)
+SONATA_BASE_CFG = dict(
+    type="Sonata-v1m1",
+    backbone=dict(
+        type="PT-v3m2", in_channels=9, order=("z", "z-trans", "hilbert", "hilbert-trans"), stride=(2, 2, 2, 2),
+        enc_depths=(3, 3, 3, 12, 3), enc_channels=(48, 96, 192, 384, 512), enc_num_head=(3, 6, 12, 24, 32),
+        enc_patch_size=(1024, 1024, 1024, 1024, 1024), mlp_ratio=4, qkv_bias=True, qk_scale=None, attn_drop=0.0,
+        proj_drop=0.0, drop_path=0.3, shuffle_orders=True, pre_norm=True, enable_rpe=False, enable_flash=True,
+        upcast_attention=False, upcast_softmax=False, traceable=True, enc_mode=True, mask_token=True),
+    teacher_custom=dict(attn_drop=0.0, proj_drop=0.0, drop_path=0.0),
+    head_in_channels=1088, head_hidden_channels=4096, head_embed_channels=256, head_num_prototypes=4096,
+    num_global_view=2, num_local_view=4, mask_size_start=0.1, mask_size_base=0.4, mask_size_warmup_ratio=0.05,
+    mask_ratio_start=0.3, mask_ratio_base=0.7, mask_ratio_warmup_ratio=0.05, mask_jitter=0.01, teacher_temp_start=0.04,
+    teacher_temp_base=0.07, teacher_temp_warmup_ratio=0.05, student_temp=0.1, mask_loss_weight=2 / 8,
+    roll_mask_loss_weight=2 / 8, unmask_loss_weight=4 / 8, momentum_base=0.994, momentum_final=1, match_max_k=8,
+    match_max_r=0.32, up_cast_level=2,
+)
+SONATA_TINY_CFG = dict(
+    type="Sonata-v1m1",
+    backbone=dict(
+        type="PT-v3m2", in_channels=4, order=("z", "z-trans"), stride=(2, 2), enc_depths=(1, 1, 1),
+        enc_channels=(16, 16, 32), enc_num_head=(1, 1, 2), enc_patch_size=(16, 16, 16), drop_path=0.0,
+        shuffle_orders=False, enable_flash=False, traceable=True, enc_mode=True, mask_token=True),
+    head_in_channels=64, head_hidden_channels=64, head_embed_channels=16, head_num_prototypes=100,
+    num_global_view=2, num_local_view=2, mask_size_start=1.0, mask_ratio_start=0.5, mask_jitter=None,
+    match_max_r=0.04, up_cast_level=2,
+)

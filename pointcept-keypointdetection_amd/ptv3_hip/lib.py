@@ -248,6 +248,15 @@ SIGNATURES = {
     "ptv3_cac_distill_bwd": (c_int, [P, P, P, P, P, c_int64, c_int, P, P]),
     "ptv3_ppt_head_capable": (c_int, [c_int, c_int]),
     "ptv3_ppt_head_fwd": (c_int, [P, P, P, c_float, c_float, c_int64, c_int, c_int, P, P]),
+    "ptv3_sonata_capable": (c_int, [c_int]),
+    "ptv3_sonata_sk_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "ptv3_sonata_sk_pass": (c_int, [P, c_int, P, c_int, c_int64, c_int64, c_int, c_double, P, c_double, P, P, P, c_size_t,
+                                    P]),
+    "ptv3_sonata_ce_workspace_bytes": (c_size_t, [c_int64]),
+    "ptv3_sonata_ce_fwd": (c_int, [P, c_int, P, c_int, c_int64, P, c_int, P, c_int, c_int64, c_int64, c_int, c_double,
+                                   c_double, P, P, c_int, P, P, P, P, P, c_size_t, P]),
+    "ptv3_sonata_ce_bwd": (c_int, [P, P, c_int, P, c_int, c_int64, P, c_int, P, c_int, c_int64, c_int64, c_int, c_double,
+                                   c_double, P, P, P, P, c_int, P, P, P]),
 }
 
 

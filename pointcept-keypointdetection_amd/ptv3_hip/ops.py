@@ -1687,6 +1687,109 @@ def cac_distill_bwd(dloss, pred, soft, labels, coef):
 
 
 # ---------------------------------------------------------------------------------------------
+# Sonata self-distillation loss (csrc/sonata_loss.hip)
+# ---------------------------------------------------------------------------------------------
+def sonata_capable(k):
+    """K prototypes ptv3_sonata_* cover: 2 <= K <= 4096."""
+    return bool(lib.ptv3_sonata_capable(int(k)))
+
+
+def _sonata_scale(who, value, name):
+    value = float(value)
+    if not (value > 0.0 and value < float("inf")):
+        raise RuntimeError(f"{who}: {name} must be finite and positive, got {value}")
+    return value
+
+
+def _sonata_rows(who, logits, idx, name):
+    _chk(logits, f"{who}: {name}", _F, 2)
+    _chk(idx, f"{who}: idx_{name}", (torch.int32, torch.int64), 1)
+    if logits.shape[0] == 0 and idx.shape[0] > 0:
+        raise RuntimeError(f"{who}: {name} has no rows to gather from")
+    return int(idx.dtype == torch.int32)
+
+
+def sonata_sk_pass(x, idx_t, inv_temp, u=None, n_total=None, with_u=True):
+    """One Sinkhorn-Knopp sweep over the gathered teacher logits x[idx_t] (never written): (A, u_next), both (K) fp32.
+    u None: A[k] = sum_m exp(x[idx_t[m], k] / T).  Otherwise A[k] = sum_m E[m, k] / (n_total d[m]), d = E u.  A is the
+    local sum; u_next = 1 / (K A) serves a caller with one rank (None with with_u=False or M = 0).  exp is taken without
+    a shift as the reference does: cosine logits and T >= 0.04 keep |x / T| <= 25."""
+    who = "sonata_sk_pass"
+    i32 = _sonata_rows(who, x, idx_t, "x")
+    inv_temp = _sonata_scale(who, inv_temp, "1 / T")
+    _chk(u, f"{who}: u", torch.float32, 1)
+    nt, k = x.shape
+    m = idx_t.shape[0]
+    if u is not None and (u.shape[0] != k or n_total is None or n_total < m):
+        raise RuntimeError(f"{who}: u must hold K values and n_total count the pairs of all ranks")
+    dev = x.device
+    if m == 0:
+        return torch.zeros(k, dtype=torch.float32, device=dev), None
+    a = torch.empty(k, dtype=torch.float32, device=dev)
+    u_next = torch.empty(k, dtype=torch.float32, device=dev) if with_u else None
+    nbytes = lib.ptv3_sonata_sk_workspace_bytes(m, k)
+    ws = _ws(nbytes, dev)
+    lib.check(lib.ptv3_sonata_sk_pass(_p(x), _dt(x), _p(idx_t), i32, nt, m, k, inv_temp, _p(u),
+                                      float(n_total if u is not None else m), _p(a), _p(u_next), _p(ws), nbytes,
+                                      _stream()), "ptv3_sonata_sk_pass")
+    return a, u_next
+
+
+def _sonata_ce_args(who, x, idx_t, u, s, idx_s, offset_s):
+    t32 = _sonata_rows(who, x, idx_t, "x")
+    s32 = _sonata_rows(who, s, idx_s, "s")
+    _chk(u, f"{who}: u", torch.float32, 1)
+    off = _scene_offset(offset_s, "offset_s")
+    k = x.shape[1]
+    if s.shape[1] != k or u.shape[0] != k or idx_s.shape[0] != idx_t.shape[0] or idx_s.shape[0] > s.shape[0]:
+        raise RuntimeError(f"{who}: x {tuple(x.shape)} / s {tuple(s.shape)} / u {tuple(u.shape)} / pairs "
+                           f"{idx_t.shape[0]}, {idx_s.shape[0]}: expected (Nt, K), (Ns, K), (K) and M <= Ns pairs")
+    return t32, s32, off, k
+
+
+def sonata_ce(x, idx_t, inv_temp, u, s, idx_s, inv_tau, offset_s):
+    """The loss of one pairing: (loss (1), d (M), lse (M), gscale (nb)), all fp32.  target[m] = E[m] u / d[m] is formed
+    on the fly, log_softmax(s[idx_s[m]] / tau) likewise; pairs are averaged per scene of offset_s (the student's), then
+    the scenes up to the last one that has a pair.  idx_s must be strictly increasing.  M = 0: zeros, nothing launched."""
+    who = "sonata_ce"
+    t32, s32, off, k = _sonata_ce_args(who, x, idx_t, u, s, idx_s, offset_s)
+    inv_temp, inv_tau = _sonata_scale(who, inv_temp, "1 / T"), _sonata_scale(who, inv_tau, "1 / tau")
+    dev, m, nb = x.device, idx_t.shape[0], off.shape[0]
+    if m == 0:
+        z = torch.zeros(0, dtype=torch.float32, device=dev)
+        return torch.zeros(1, dtype=torch.float32, device=dev), z, z.clone(), torch.zeros(nb, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    d = torch.empty(m, dtype=torch.float32, device=dev)
+    lse = torch.empty(m, dtype=torch.float32, device=dev)
+    gscale = torch.empty(nb, dtype=torch.float32, device=dev)
+    nbytes = lib.ptv3_sonata_ce_workspace_bytes(m)
+    ws = _ws(nbytes, dev)
+    lib.check(lib.ptv3_sonata_ce_fwd(_p(x), _dt(x), _p(idx_t), t32, x.shape[0], _p(s), _dt(s), _p(idx_s), s32, s.shape[0],
+                                     m, k, inv_temp, inv_tau, _p(u), _p(off), nb, _p(loss), _p(d), _p(lse), _p(gscale),
+                                     _p(ws), nbytes, _stream()), "ptv3_sonata_ce_fwd")
+    return loss, d, lse, gscale
+
+
+def sonata_ce_bwd(dloss, x, idx_t, inv_temp, u, s, idx_s, inv_tau, offset_s, d, lse, gscale):
+    """ds (Ns, K) in the dtype of s; exact zeros in the rows idx_s leaves out.  The teacher gets no gradient."""
+    who = "sonata_ce_bwd"
+    t32, s32, off, k = _sonata_ce_args(who, x, idx_t, u, s, idx_s, offset_s)
+    inv_temp, inv_tau = _sonata_scale(who, inv_temp, "1 / T"), _sonata_scale(who, inv_tau, "1 / tau")
+    m, nb = idx_t.shape[0], off.shape[0]
+    for t, name, size in ((dloss, "dloss", 1), (d, "d", m), (lse, "lse", m), (gscale, "gscale", nb)):
+        _chk(t, f"{who}: {name}", torch.float32)
+        if t.numel() != size:
+            raise RuntimeError(f"{who}: {name} must hold {size} values")
+    if m == 0:
+        return torch.zeros_like(s)
+    ds = torch.empty_like(s)
+    lib.check(lib.ptv3_sonata_ce_bwd(_p(dloss), _p(x), _dt(x), _p(idx_t), t32, x.shape[0], _p(s), _dt(s), _p(idx_s), s32,
+                                     s.shape[0], m, k, inv_temp, inv_tau, _p(u), _p(d), _p(lse), _p(off), nb, _p(gscale),
+                                     _p(ds), _stream()), "ptv3_sonata_ce_bwd")
+    return ds
+
+
+# ---------------------------------------------------------------------------------------------
 # language-guided head of Point Prompt Training (csrc/ppt_head.hip)
 # ---------------------------------------------------------------------------------------------
 def ppt_head_capable(c, k):
