@@ -25,6 +25,12 @@ extern "C" {
 #define PTV3_F32 0
 #define PTV3_BF16 1
 
+/* return codes */
+#define PTV3_OK 0
+#define PTV3_ERR_ARG 1         /* a malformed call */
+#define PTV3_ERR_LAUNCH 2      /* a kernel launch failed */         
+#define PTV3_ERR_UNSUPPORTED 3 /* a well-formed shape no kernel serves */
+
 /* curve ids for ptv3_sfc_encode (pointcept/models/utils/serialization/default.py:9-24) */
 #define PTV3_ORDER_Z 0
 #define PTV3_ORDER_Z_TRANS 1

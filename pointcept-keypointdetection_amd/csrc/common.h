@@ -4,13 +4,7 @@
 #include <stdint.h>
 #include <mutex>
 
-#define PTV3_OK 0
-#define PTV3_ERR_ARG 1
-#define PTV3_ERR_LAUNCH 2
-#define PTV3_ERR_UNSUPPORTED 3
-
-#define PTV3_F32 0
-#define PTV3_BF16 1
+#include "../../include/ptv3_hip.h"   // PTV3_OK / PTV3_ERR_*, PTV3_F32 / PTV3_BF16
 
 namespace ptv3 {
 

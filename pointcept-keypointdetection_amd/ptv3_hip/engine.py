@@ -1,40 +1,12 @@
 """Python side of ptv3_forward (include/ptv3_hip.h): packs a PT-v3m1 module tree into the flat
 parameter table + model description the native executor walks, and runs one forward with it."""
 import ctypes
-from ctypes import c_float, c_int32, c_int64, c_void_p, POINTER
+from ctypes import addressof, c_int32, c_int64, c_void_p
 
 import torch
 
-from .lib import lib, PTV3_F32, PTV3_BF16, ORDER_IDS
+from .lib import lib, PTV3_F32, PTV3_BF16, ORDER_IDS, ptv3_model_desc, ptv3_forward_io
 from . import ops
-
-
-class ModelDesc(ctypes.Structure):
-    _fields_ = [("dtype", c_int32), ("in_channels", c_int32), ("num_stages", c_int32), ("num_orders", c_int32),
-                ("enc_depths", c_int32 * 8), ("enc_channels", c_int32 * 8), ("enc_heads", c_int32 * 8),
-                ("enc_patch", c_int32 * 8), ("dec_depths", c_int32 * 8), ("dec_channels", c_int32 * 8),
-                ("dec_heads", c_int32 * 8), ("dec_patch", c_int32 * 8), ("stride", c_int32 * 8),
-                ("enc_mode", c_int32), ("enable_flash", c_int32), ("head_hidden", c_int32), ("head_out", c_int32),
-                ("mlp_ratio", c_float), ("ln_eps", c_float), ("qk_scale", c_float)]
-
-
-class ForwardIO(ctypes.Structure):
-    _fields_ = [("grid_coord", c_void_p), ("coord_is_i64", c_int32), ("feat", c_void_p), ("batch", c_void_p),
-                ("offset", c_void_p), ("offset_host", POINTER(c_int64)), ("b", c_int32), ("n", c_int64),
-                ("depth", c_int32), ("order_ids_host", POINTER(c_int32)), ("pool_perm_host", POINTER(c_int32)),
-                ("code", c_void_p), ("order", c_void_p), ("inverse", c_void_p), ("out_feat", c_void_p),
-                ("out_head", c_void_p), ("stage_points_host", POINTER(c_int64)), ("depth_out", POINTER(c_int32)),
-                ("batch_out", c_void_p), ("inputs_resident", c_int32), ("overlap_calls", c_int32),
-                ("raw_feat", c_void_p), ("raw_feat_channels", c_int32), ("raw_feat_dtype", c_int32),
-                ("arena_n", c_int64), ("arena_b", c_int32), ("executor", c_void_p)]
-
-
-def declare(dll):
-    dll.ptv3_forward_workspace_bytes.restype = ctypes.c_size_t
-    dll.ptv3_forward_workspace_bytes.argtypes = [POINTER(ModelDesc), c_int64, ctypes.c_int]
-    dll.ptv3_forward.restype = ctypes.c_int
-    dll.ptv3_forward.argtypes = [POINTER(ModelDesc), POINTER(c_void_p), ctypes.c_int, POINTER(ForwardIO), c_void_p,
-                                 ctypes.c_size_t, c_void_p]
 
 
 class Executor:
@@ -190,7 +162,7 @@ def eligible(backbone, head=None):
 
 
 def _desc(bb, head, dtype, cin_pad):
-    d = ModelDesc()
+    d = ptv3_model_desc()
     d.dtype = PTV3_F32 if dtype == torch.float32 else PTV3_BF16
     d.in_channels = cin_pad
     d.num_stages = bb.num_stages
@@ -225,9 +197,6 @@ def forward(backbone, point, dtype, head=None):
     """Runs the native executor.  `point` is a Point with feat (already `dtype`), grid_coord, batch, offset.
     Fills the Point like the module path does and returns (point, head_out or None)."""
     dll = lib.load()
-    if not hasattr(dll, "_engine_declared"):
-        declare(dll)
-        dll._engine_declared = True
     cache = backbone.__dict__.setdefault("_engine_packed", {})
     key = (dtype, id(head))
     if key not in cache:
@@ -343,7 +312,7 @@ def forward(backbone, point, dtype, head=None):
         with torch.cuda.device(dev):   # an executor binds to the device that is current when it is created
             execs[dev] = Executor()
     stage_pts = (c_int64 * 8)()
-    io = ForwardIO()
+    io = ptv3_forward_io()
     io.executor = execs[dev].handle
     io.grid_coord, io.coord_is_i64 = gc.data_ptr(), int(gc.dtype == torch.int64)
     io.feat, io.offset = feat.data_ptr(), offset.data_ptr()
@@ -361,13 +330,15 @@ def forward(backbone, point, dtype, head=None):
         io.batch, io.batch_out = batch.data_ptr(), None
     depth_out = c_int32(0)
     io.offset_host, io.b, io.n, io.depth = None, nb, n, 0
-    io.depth_out = ctypes.pointer(depth_out)
+    # host-side fields: a c_void_p field takes an address; order_ids, perm_arr, stage_pts and depth_out stay alive as
+    # locals until ptv3_forward returns
+    io.depth_out = addressof(depth_out)
     io.inputs_resident = int(bool(getattr(backbone, "inputs_resident", False)))
-    io.order_ids_host, io.pool_perm_host = order_ids, perm_arr
+    io.order_ids_host, io.pool_perm_host = addressof(order_ids), addressof(perm_arr)
     io.code, io.order, io.inverse = code.data_ptr(), order.data_ptr(), inverse.data_ptr()
     io.out_feat = out_feat.data_ptr()
     io.out_head = out_head.data_ptr() if out_head is not None else None
-    io.stage_points_host = stage_pts
+    io.stage_points_host = addressof(stage_pts)
     rc = dll.ptv3_forward(ctypes.byref(desc), pk.table, len(pk.tensors), ctypes.byref(io), arena.data_ptr(),
                           arena.numel(), ops._stream())
     lib.check(rc, "ptv3_forward")

@@ -9,6 +9,11 @@ from types import SimpleNamespace
 import torch
 
 from .lib import lib, PTV3_F32, PTV3_BF16, ACT_NONE, ACT_GELU, ACT_RELU, ORDER_IDS  # noqa: F401
+from .lib import PTV3_ERR_UNSUPPORTED, PTV3_PG_TRUNCATED
+from .lib import PTV3_HASH_FNV as HASH_FNV, PTV3_HASH_RAVEL as HASH_RAVEL  # noqa: F401
+from .lib import (PTV3_KP_ARGMAX as KP_ARGMAX, PTV3_KP_WEIGHTED as KP_WEIGHTED,  # noqa: F401
+                  PTV3_KP_GT_MEAN as KP_GT_MEAN, PTV3_KP_GT_FIRST as KP_GT_FIRST)
+from .lib import PTV3_CLS_HEAD_ROW_TILE as CLS_HEAD_ROW_TILE  # noqa: F401
 
 _DT = {torch.float32: PTV3_F32, torch.bfloat16: PTV3_BF16}
 
@@ -300,7 +305,7 @@ def window_attention_rpe(qkv, win_order, win_inverse, heads, patch, scale, grid_
     rc = lib.ptv3_window_attn_rpe_fwd(_p(qkv), _p(win_order), _p(win_inverse), _p(out), n, n_pad, c, int(heads),
                                       int(patch), float(scale), _p(grid_coord), _p(rpe_table), int(pos_bnd), _dt(qkv),
                                       _stream())
-    if rc == 3:   # PTV3_ERR_UNSUPPORTED
+    if rc == PTV3_ERR_UNSUPPORTED:
         return None
     lib.check(rc, "ptv3_window_attn_rpe_fwd")
     return out
@@ -1077,9 +1082,6 @@ def window_attention_rpe_bwd(qkv, out, dout, win_order, win_inverse, heads, patc
 # ---------------------------------------------------------------------------------------------
 # GridSample (before the model)
 # ---------------------------------------------------------------------------------------------
-HASH_FNV, HASH_RAVEL = 0, 1
-
-
 def grid_hash(coord, grid_size, hash_type=HASH_FNV):
     """-> grid_coord (n,3) int64 (minimum subtracted), min_max (6) int64, key (n) int64 holding the uint64 hash."""
     _chk(coord, "coord", torch.float32, 2)
@@ -1189,9 +1191,6 @@ def swin_attention_bwd(q, k, v, dout, q_table, k_table, v_table, table_offsets, 
 # ---------------------------------------------------------------------------------------------
 # keypoint aggregation (after the model)
 # ---------------------------------------------------------------------------------------------
-KP_ARGMAX, KP_WEIGHTED, KP_GT_MEAN, KP_GT_FIRST = 0, 1, 2, 3
-
-
 def keypoint_aggregate(coord, pred, offset, mode, scale=None, centroid=None, thresh=0.5):
     """(B, K, 3) keypoints + (B, K) int32 aux per scene and keypoint; see ptv3_keypoint_aggregate."""
     _chk(coord, "coord", torch.float32, 2)
@@ -1274,9 +1273,6 @@ def scene_mean_bwd(dg, offset, n, dtype):
 # ---------------------------------------------------------------------------------------------
 # classifier / regressor head (DefaultClassifier, PigBodyRegressor)
 # ---------------------------------------------------------------------------------------------
-CLS_HEAD_ROW_TILE = 8   # PTV3_CLS_HEAD_ROW_TILE
-
-
 def cls_head_capable(c, h1, h2, out):
     """True when the batch head kernels take these widths (ptv3_cls_head_capable)."""
     return bool(lib.ptv3_cls_head_capable(int(c), int(h1), int(h2), int(out)))
@@ -2727,7 +2723,7 @@ def octree_attention(qkv, xyz, batch, rpe_table, heads, patch, dilation, pos_bnd
         out = torch.empty((n_t, c), dtype=torch.float32, device=qkv.device)
         rc = lib.ptv3_octree_attn_fwd(_p(qkv), _p(xyz), _p(batch), _p(table), _p(out), n_t, c, int(heads), int(patch),
                                       int(dilation), int(pos_bnd), float(scale), _stream())
-        if rc != 3:   # PTV3_ERR_UNSUPPORTED: a shape for the composition
+        if rc != PTV3_ERR_UNSUPPORTED:   # else: a shape for the composition
             lib.check(rc, "ptv3_octree_attn_fwd")
             return out
     return octree_attention_torch(qkv, xyz, batch, rpe_table, heads, patch, dilation, pos_bnd, scale, pad_row)
@@ -2799,7 +2795,6 @@ def pg_cluster(xyz, label, offsets, radius, min_points, propose_points=0):
     None when a point has more than 1000 neighbours (PTV3_PG_TRUNCATED: the union is not the reference's directed search
     there; take pg_ballquery_batch_p + pg_bfs_cluster_host).  n_large: clusters with more than propose_points members.
     One synchronisation."""
-    from .lib import PTV3_PG_TRUNCATED
     n, b, ws, ws_bytes = _pg_args("pg_cluster", xyz, offsets)
     _chk(label, "label", torch.int32, 1)
     if label.shape[0] != n:

@@ -1,8 +1,10 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads and exports every declared symbol,
 the registry / builder / state_dict surface matches the reference, and the product path refuses to run
 without a GPU (no CPU fallback)."""
+import ctypes
 import os
 import re
+import shutil
 
 import pytest
 import torch
@@ -26,6 +28,136 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert getattr(dll, name) is not None
     assert dll.ptv3_version() >= 100
+
+
+def _host_cxx():
+    """A C++ compiler for host code: $CXX, the usual names, else the Makefile's hipcc (a .cpp is host code to it)."""
+    makefile = open(os.path.join(ROOT, "pointcept-keypointdetection_amd", "Makefile")).read()
+    hipcc = re.search(r"^HIPCC \?= (\S+)", makefile, re.M).group(1)
+    for cxx in (os.environ.get("CXX"), "c++", "g++", "clang++", hipcc):
+        if cxx and shutil.which(cxx):
+            return shutil.which(cxx)
+    return None
+
+
+def _type_code(t):
+    """Class code of a ctypes type as _ABI_PROBE prints it: v, p, f<bytes>, i<bytes> / u<bytes>."""
+    if t is None:
+        return "v"
+    if t in (ctypes.c_void_p, ctypes.c_char_p):
+        return "p"
+    if t in (ctypes.c_float, ctypes.c_double):
+        return f"f{ctypes.sizeof(t)}"
+    return f"{'i' if t(-1).value < 0 else 'u'}{ctypes.sizeof(t)}"
+
+
+_ABI_PROBE = r"""
+#include <cstddef>
+#include <cstdio>
+#include <type_traits>
+#include "ptv3_hip.h"
+template <class T> void code() {
+  typedef typename std::conditional<std::is_void<T>::value, char, T>::type sized;
+  if (std::is_void<T>::value) std::printf(" v");
+  else if (std::is_pointer<T>::value) std::printf(" p");
+  else if (std::is_floating_point<T>::value) std::printf(" f%zu", sizeof(sized));
+  else if (std::is_integral<T>::value) std::printf(" %c%zu", std::is_signed<T>::value ? 'i' : 'u', sizeof(sized));
+  else std::printf(" ?");
+}
+template <class F> struct sig;
+template <class R, class... A> struct sig<R (*)(A...)> {   // from decltype(&name): no symbol is referenced
+  static void print(const char* name) {
+    std::printf("%s", name);
+    code<R>();
+    int each[] = {0, (code<A>(), 0)...};
+    (void)each;
+    std::printf("\n");
+  }
+};
+#define FN(name) sig<decltype(&name)>::print(#name);
+#define STRUCT(name) std::printf(#name " %zu\n", sizeof(name));
+#define FIELD(name, f) std::printf(#name "." #f " %zu %zu\n", offsetof(name, f), sizeof(((name*)0)->f));
+#define DEFINE(name) std::printf(#name " %lld\n", (long long)(name));
+int main() {
+"""
+
+
+def test_compiler_agrees_with_the_derived_binding(tmp_path):
+    """What ptv3_hip/lib.py derives from the header's text against what a C++ compiler makes of the same header: the
+    class and width of every return and parameter type (pointer / float / signed or unsigned integer / void), sizeof
+    every struct, offset and size of every field, the value of every integer define.  The names of functions, structs
+    and defines come from regexes of this file, not from the binding, so a declaration the binding lost fails too."""
+    import subprocess
+    import importlib
+    L = importlib.import_module("ptv3_hip.lib")   # the module: ptv3_hip.lib, the attribute, is its handle object
+    cxx = _host_cxx()
+    if cxx is None:
+        pytest.skip("no C++ compiler on this machine")
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ptv3_hip.h")).read(), flags=re.S)
+    functions = _declared_symbols()
+    structs = re.findall(r"\}\s*(\w+)\s*;", text)
+    defines = re.findall(r"^#define[ \t]+(PTV3_\w+)[ \t]+\S", text, re.M)
+    assert set(functions) == set(L.SIGNATURES)
+    assert len(structs) == 5 and set(structs) == set(L.STRUCTS)
+    assert len(defines) >= 21 and set(defines) == set(L.DEFINES)
+    body, want = [], []
+    for name in functions:
+        res, args = L.SIGNATURES[name]
+        body.append(f"FN({name})")
+        want.append(" ".join([name, _type_code(res)] + [_type_code(a) for a in args]))
+    for name in structs:
+        cls = L.STRUCTS[name]
+        body.append(f"STRUCT({name})")
+        want.append(f"{name} {ctypes.sizeof(cls)}")
+        for field, _ in cls._fields_:
+            body.append(f"FIELD({name}, {field})")
+            want.append(f"{name}.{field} {getattr(cls, field).offset} {getattr(cls, field).size}")
+    for name in defines:
+        body.append(f"DEFINE({name})")
+        want.append(f"{name} {L.DEFINES[name]}")
+    src, exe = tmp_path / "abi_probe.cpp", tmp_path / "abi_probe"
+    src.write_text(_ABI_PROBE + "\n".join(body) + "\n}\n")
+    r = subprocess.run([cxx, "-std=c++14", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    got = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60, check=True).stdout.splitlines()
+    assert len(got) == len(want)
+    wrong = [(g, w) for g, w in zip(got, want) if g != w]
+    assert not wrong, wrong[:10]
+
+
+@pytest.mark.parametrize("name,snippet", [
+    ("ptv3_a", "int ptv3_ok(int x);\nint ptv3_a(unsigned x, void* stream);"),                    # unknown scalar type
+    ("ptv3_b", "int ptv3_b(int (*callback)(int), void* stream);"),                              # function pointer
+    ("ptv3_c", "typedef struct { int32_t n; int32_t flags : 3; } ptv3_c;"),                     # bit-field
+    ("ptv3_d", "typedef struct { struct { int a; } inner; int b; } ptv3_d;"),                   # nested struct
+    ("ptv3_e", "int ptv3_ok(int x);\nint ptv3_e(int x)\n"),                                     # unterminated, at the end
+    ("ptv3_f", "int ptv3_f(int x)\nint ptv3_ok(int x);"),                                       # unterminated, inside
+    ("PTV3_G", "#define PTV3_G (1 << 4)\nint ptv3_ok(int x);"),                                 # not a plain integer
+])
+def test_header_parser_refuses_what_it_cannot_bind(name, snippet):
+    from ptv3_hip.lib import parse_header
+    functions, structs, defines = parse_header("int ptv3_ok(int x);\n#define PTV3_OK 0\n")
+    assert list(functions) == ["ptv3_ok"] and not structs and defines == {"PTV3_OK": 0}
+    with pytest.raises(ValueError, match=name):
+        parse_header(snippet)
+
+
+def test_derived_structs_construct_positionally_in_header_order():
+    """autograd.py and ops.py fill ptv3_block_train and ptv3_cls_head_params positionally: field order is the contract.
+    The positions asserted are counted in include/ptv3_hip.h by hand."""
+    import importlib
+    L = importlib.import_module("ptv3_hip.lib")   # the module: ptv3_hip.lib, the attribute, is its handle object
+    assert L.ClsHeadParams is L.ptv3_cls_head_params and L.BlockTrain is L.ptv3_block_train
+    assert L.ClsHeadGrads is L.ptv3_cls_head_grads
+    p = L.ptv3_cls_head_params(*range(1, 19))
+    assert (p.w1, p.bn2_running_mean, p.bn2_eps) == (1, 11, 18.0)
+    with pytest.raises(TypeError):
+        L.ptv3_cls_head_params(*range(1, 20))
+    b = L.ptv3_block_train(*range(1, 81))
+    assert (b.n, b.sum_len_sq, b.w_qkv, b.workspace_bytes, b.attn_lse) == (1, 15.0, 25, 79, 80)
+    with pytest.raises(TypeError):
+        L.ptv3_block_train(*range(1, 82))
 
 
 def test_argument_validation_without_gpu():
