@@ -1330,6 +1330,54 @@ int ptv3_sonata_ce_bwd(const float* dloss, const void* x, int x_dtype, const voi
                        double inv_temp, double inv_tau, const float* u, const float* d, const float* lse,
                        const int64_t* offset_s, int nb, const float* gscale, void* ds, void* stream);
 
+/* Image branch of "Concerto-v1m1", pointcept/models/concerto/concerto_v1m1_base.py:529-573 and :781-845
+ * (csrc/concerto.hip).  No atomics anywhere: every reduction runs in a fixed order, two runs are
+ * bitwise equal; nothing is read back by the host.
+ * ptv3_concerto_pool_corr: one pooling level of the pixel correspondences.  corr_in (n_in, V, 2) fp32, order (n_in) and
+ *   seg_start (n_out + 1) of the pooling (its children in cluster order), out (n_out, V, 2) fp32.  Per cluster and view:
+ *   count = children with BOTH entries != -1; sum over ALL children with every entry == -1 replaced by 0, elementwise;
+ *   out = sum / count, or (-1, -1) when count == 0.  Sums in float64, rounded to fp32 once: the result does not depend
+ *   on the order inside a segment.  An `order` entry outside [0, n_in) is skipped.
+ * ptv3_concerto_pair_keys: key (R * V + 1) int64 of the pairs (r, v) in that order, r a position in `rows` (R feature
+ *   rows, ascending), scene (R) the scene of each, img_base (ns) the first image of a scene.  A pair is valid when ANY of
+ *   corr[rows[r], v] is != -1; its key is the patch (img_base[scene[r]] + v) * patch_h * patch_w + trunc(c0) * patch_w +
+ *   trunc(c1), or n_patches when that lies outside [0, n_patches) (a violated precondition, kept in one bucket that the
+ *   caller can see); an invalid pair and the extra last entry get PTV3_CONCERTO_NO_PATCH, above every patch.
+ * ptv3_concerto_plan_finish: from the stable argsort `order` of the keys and its run starts seg_start (>= U + 1):
+ *   patch_ids (U) = the key of each of the first U runs, pair_row (R * V) = rows[order[i] / V], the feature row of the
+ *   i-th pair by (patch, r, v); entries behind seg_start[U] belong to no patch.
+ * ptv3_concerto_patch_mean_fwd: mean (U, C) fp32, mean[j] = the mean of feat[pair_row[i]], seg_start[j] <= i <
+ *   seg_start[j + 1], added in that order in fp32.  feat (n, C) fp32 (PTV3_F32) or bf16 (PTV3_BF16); a row outside
+ *   [0, n) is clamped.  Rows are read 4 columns at a time when C is a multiple of 4 and feat 16-byte aligned.
+ * ptv3_concerto_patch_mean_bwd: dfeat (n, C) in `dtype`, EVERY row written: the sum over v of dmean[slot[r * V + v]] /
+ *   count[slot] (slot < U, v ascending) for the rows in `rows` (found by bisection), zeros elsewhere.  slot (>= R * V)
+ *   is the run of each pair in (r, v) order.
+ * ptv3_concerto_cos_*: a (U, D) fp32 / bf16, b (nb, D) fp32 / bf16 read at row patch_ids[j] (clamped to [0, nb)).  With
+ *   shift != 0 both rows lose their mean over D.  cos[j] = a . b / (max(|a|, 1e-6) max(|b|, 1e-6)), loss[0] =
+ *   10 mean_j (1 - cos[j]) (rows added in two fixed-order stages in float64).  Means, centred rows, dot product and norms
+ *   are float64.  stats (U, 4) fp32 = mean of a, mean of b, |a'|, |b'| of the shifted rows, for the caller to look at.
+ *   bwd: da (U, D) in a's dtype = -10 dloss[0] / U (b' - (a' . b' / |a'|^2) a') / (max(|a'|, eps) max(|b'|, eps)), without
+ *   the second term on a's eps branch; the statistics are formed again in float64 from the rows, which the kernel holds
+ *   in registers (one pass over a and b); b gets no gradient.
+ * ptv3_concerto_cos_capable: 1 <= D <= 2048 (a row lives in the registers of one wavefront). */
+#define PTV3_CONCERTO_NO_PATCH 0x4000000000000000
+int ptv3_concerto_pool_corr(const float* corr_in, const int64_t* order, const int32_t* seg_start, int64_t n_in,
+                            int64_t n_out, int V, float* out, void* stream);
+int ptv3_concerto_pair_keys(const float* corr, int64_t n, const int64_t* rows, const int64_t* scene, int64_t R, int V,
+                            const int64_t* img_base, int ns, int patch_h, int patch_w, int64_t n_patches, int64_t* key,
+                            void* stream);
+int ptv3_concerto_plan_finish(const int64_t* key, const int64_t* order, const int32_t* seg_start, const int64_t* rows,
+                              int64_t R, int V, int64_t U, int64_t* patch_ids, int64_t* pair_row, void* stream);
+int ptv3_concerto_patch_mean_fwd(const void* feat, int dtype, int64_t n, int C, const int64_t* pair_row,
+                                 const int32_t* seg_start, int64_t U, float* mean, void* stream);
+int ptv3_concerto_patch_mean_bwd(const float* dmean, const int64_t* rows, const int64_t* slot, const int32_t* seg_start,
+                                 int64_t n, int64_t R, int V, int64_t U, int C, void* dfeat, int dtype, void* stream);
+int ptv3_concerto_cos_capable(int D);
+int ptv3_concerto_cos_fwd(const void* a, int a_dtype, const void* b, int b_dtype, const int64_t* patch_ids, int64_t U,
+                          int64_t nb, int D, int shift, float* cos, float* stats, float* loss, void* stream);
+int ptv3_concerto_cos_bwd(const float* dloss, const void* a, int a_dtype, const void* b, int b_dtype,
+                          const int64_t* patch_ids, int64_t U, int64_t nb, int D, int shift, void* da, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,3 +31,4 @@ from .point_group import PointGroup, PointGroupV1m2  # noqa: F401
 from .context_aware_classifier import CACSegmentor  # noqa: F401
 from .point_prompt_training import PDNorm, PointPromptTraining, PointPromptTrainingDecoupled  # noqa: F401
 from .sonata import OnlineCluster, Sonata  # noqa: F401
+from .concerto import Concerto  # noqa: F401

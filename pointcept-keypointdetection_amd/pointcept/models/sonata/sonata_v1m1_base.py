@@ -286,9 +286,10 @@ class Sonata(PointModel):
         rolled["batch"] = offset2batch(offset, perm.shape[0])
         return Point(rolled)
 
-    def up_cast(self, point):
-        """features of the last `up_cast_level` pooling stages carried back to the points they were pooled from"""
-        for _ in range(self.up_cast_level):
+    def up_cast(self, point, levels=None):
+        """features of the last `levels` (default `up_cast_level`) pooling stages carried back to the points they were
+        pooled from"""
+        for _ in range(self.up_cast_level if levels is None else levels):
             assert "pooling_parent" in point.keys()
             assert "pooling_inverse" in point.keys()
             parent = point.pop("pooling_parent")

@@ -631,6 +631,50 @@ def sonata_loss(s, x, idx_t, idx_s, offset_s, temp, student_temp, n_total=None, 
     return SonataCeFn.apply(s, x.detach(), idx_t, idx_s, offset_s, u, 1.0 / temp, 1.0 / student_temp)
 
 
+class ConcertoPatchMeanFn(Function):
+    """Mean of the feature rows over the pairs of every occupied image patch (ops.concerto_patch_mean); the backward
+    writes every row of the feature gradient from its one owner."""
+
+    @staticmethod
+    def forward(ctx, feat, plan):
+        feat = feat.contiguous()
+        ctx.plan, ctx.dtype = plan, feat.dtype
+        return ops.concerto_patch_mean(feat, plan)
+
+    @staticmethod
+    def backward(ctx, dmean):
+        return ops.concerto_patch_mean_bwd(dmean.float().contiguous(), ctx.plan, ctx.dtype), None
+
+
+class ConcertoCosFn(Function):
+    """10 mean_j (1 - cos(a[j], b[patch_ids[j]])) with both rows centred over D (ops.concerto_cos); only the inputs are
+    saved, the backward launch forms the row statistics again.  The gradient goes to a alone."""
+
+    @staticmethod
+    def forward(ctx, a, b, patch_ids, shift):
+        a, b, patch_ids = a.contiguous(), b.contiguous(), patch_ids.contiguous()
+        loss, _, _ = ops.concerto_cos(a, b, patch_ids, shift)
+        ctx.save_for_backward(a, b, patch_ids)
+        ctx.shift = shift
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        a, b, patch_ids = ctx.saved_tensors
+        da = ops.concerto_cos_bwd(dloss.float().contiguous().view(1), a, b, patch_ids, ctx.shift)
+        return da, None, None, None
+
+
+def concerto_patch_mean(feat, plan):
+    """-> (u, C) fp32 with grad to feat"""
+    return ConcertoPatchMeanFn.apply(feat, plan)
+
+
+def concerto_cos_loss(a, b, patch_ids, shift=True):
+    """-> loss, 0-d fp32 with grad to a"""
+    return ConcertoCosFn.apply(a, b.detach(), patch_ids, bool(shift))
+
+
 def linear(x, weight, bias=None):
     return LinearFn.apply(x, weight, bias)
 

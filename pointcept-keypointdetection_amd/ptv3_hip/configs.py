@@ -283,3 +283,29 @@ SONATA_TINY_CFG = dict(
     num_global_view=2, num_local_view=2, mask_size_start=1.0, mask_ratio_start=0.5, mask_jitter=None,
     match_max_r=0.04, up_cast_level=2,
 )
+
+# Concerto pretraining: the `model` dict of configs/concerto/pretrain-concerto-v1m1-0-base.py (Sonata's base backbone and
+# schedules; the image branch carries half of the loss), and a tiny one (four stages, the heads at level 2, the image
+# branch at level 1, 6 x 6 patches of a 24-channel encoder)
+CONCERTO_BASE_CFG = dict(
+    {k: v for k, v in SONATA_BASE_CFG.items() if k not in ("type", "head_in_channels")},
+    type="Concerto-v1m1", patch_h=518 // 14, patch_w=518 // 14, image_weight_name="dinov2_vitg14_reg",
+    image_weight_path="facebook/dinov2-with-registers-giant", backbone_out_channels=1184, embedding_channels=64,
+    student_pretrained=False, enc2d_upcast_level=3, head_in_channels=1088, enc2d_head_in_channels=1536,
+    enc2d_head_hidden_channels=4096, enc2d_head_embed_channels=256, enc2d_head_num_prototypes=4096,
+    mask_loss_weight=1 / 8, roll_mask_loss_weight=1 / 8, unmask_loss_weight=2 / 8, enc2d_loss_weight=4 / 8,
+    enc2d_cos_shift=True, sonata_model_type="online",
+)
+CONCERTO_TINY_CFG = dict(
+    type="Concerto-v1m1", image_weight_name="stub", image_weight_path=None,
+    backbone=dict(
+        type="PT-v3m2", in_channels=4, order=("z", "z-trans"), stride=(2, 2, 2), enc_depths=(1, 1, 1, 1),
+        enc_channels=(16, 16, 32, 32), enc_num_head=(1, 1, 2, 2), enc_patch_size=(16, 16, 16, 16), drop_path=0.0,
+        shuffle_orders=False, enable_flash=False, traceable=True, enc_mode=True, mask_token=True),
+    head_in_channels=64, backbone_out_channels=80, embedding_channels=16, patch_w=6, patch_h=6,
+    head_hidden_channels=64, head_embed_channels=16, head_num_prototypes=100, enc2d_head_in_channels=24,
+    enc2d_head_hidden_channels=32, enc2d_head_embed_channels=16, enc2d_head_num_prototypes=20, num_global_view=2,
+    num_local_view=2, mask_size_start=1.0, mask_ratio_start=0.5, mask_jitter=None, match_max_r=0.04,
+    mask_loss_weight=1 / 8, roll_mask_loss_weight=1 / 8, unmask_loss_weight=2 / 8, enc2d_loss_weight=4 / 8,
+    up_cast_level=1, enc2d_upcast_level=2, enc2d_cos_shift=True, sonata_model_type="online",
+)

@@ -1786,6 +1786,167 @@ def sonata_ce_bwd(dloss, x, idx_t, inv_temp, u, s, idx_s, inv_tau, offset_s, d, 
 
 
 # ---------------------------------------------------------------------------------------------
+# Concerto image branch (csrc/concerto.hip)
+# ---------------------------------------------------------------------------------------------
+class ConcertoPlan:
+    """Which principal-view rows fall into which image patch (concerto_plan).  u occupied patches; patch_ids (u) int64
+    ascending and unique; seg_start (>= u + 1) int32, the pairs of patch j are seg_start[j] .. seg_start[j + 1]; pair_row
+    (R * V) int64, the feature row of every pair ordered by (patch, row, view) - entries from seg_start[u] on belong to no
+    patch; rows (R) int64 ascending and slot (>= R * V) int64, the patch run of pair (r, v) (>= u: none); n feature rows."""
+    __slots__ = ("u", "patch_ids", "seg_start", "pair_row", "rows", "slot", "n", "views")
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def concerto_pool_corr(corr_in, order, seg_start):
+    """One pooling level of the pixel correspondences: corr_in (n_in, V, 2) fp32 (an integer tensor is converted once),
+    order (n_in) int64 and seg_start (n_out + 1) int32 of the pooling -> (n_out, V, 2) fp32.  Per cluster and view the
+    count is over the children with BOTH entries != -1, the sum over ALL children with each -1 entry read as 0, the
+    result sum / count or (-1, -1) without a counted child; float64 sums.  V = 0: an empty tensor, nothing launched."""
+    who = "concerto_pool_corr"
+    if not corr_in.is_floating_point():
+        corr_in = corr_in.float()
+    _chk(corr_in, f"{who}: corr_in", torch.float32, 3)
+    _chk(order, f"{who}: order", torch.int64, 1)
+    _chk(seg_start, f"{who}: seg_start", torch.int32, 1)
+    n_in, v, two = corr_in.shape
+    n_out = seg_start.shape[0] - 1
+    if two != 2 or order.shape[0] != n_in or n_out < 0:
+        raise RuntimeError(f"{who}: corr_in {tuple(corr_in.shape)} / order {tuple(order.shape)} / seg_start "
+                           f"{tuple(seg_start.shape)}: expected (n_in, V, 2), (n_in) and (n_out + 1)")
+    out = torch.empty((n_out, v, 2), dtype=torch.float32, device=corr_in.device)
+    if v == 0 or n_out == 0 or n_in == 0:
+        return out.fill_(-1.0)
+    lib.check(lib.ptv3_concerto_pool_corr(_p(corr_in), _p(order), _p(seg_start), n_in, n_out, v, _p(out), _stream()),
+              "ptv3_concerto_pool_corr")
+    return out
+
+
+def concerto_plan(corr, rows, scene, img_base, patch_h, patch_w, n_patches, check=False):
+    """ConcertoPlan of the final-level correspondences corr (n, V, 2) fp32: rows (R) int64 ascending are the feature rows of
+    the principal global views, scene (R) int64 their scenes, img_base (scenes) int64 the first image of each scene.  A
+    pair (row, view) is valid when ANY of its two entries is != -1; its patch is (img_base[scene] + view) * patch_h *
+    patch_w + trunc(c0) * patch_w + trunc(c1).  ptv3_concerto_pair_keys, the stable ptv3_argsort_i64 and
+    ptv3_pool_segments (whose run count is the ONE host read: u), ptv3_concerto_plan_finish.  A patch outside [0, n_patches)
+    is a violated precondition; it lands in one bucket with id n_patches, which check=True (one more read) refuses."""
+    who = "concerto_plan"
+    _chk(corr, f"{who}: corr", torch.float32, 3)
+    for t, name in ((rows, "rows"), (scene, "scene"), (img_base, "img_base")):
+        _chk(t, f"{who}: {name}", torch.int64, 1)
+    n, v, two = corr.shape
+    r = rows.shape[0]
+    if two != 2 or scene.shape[0] != r or r > n or img_base.shape[0] == 0:
+        raise RuntimeError(f"{who}: corr {tuple(corr.shape)} / rows {r} / scene {scene.shape[0]}: expected (n, V, 2) and "
+                           "R <= n rows with a scene each")
+    dev = corr.device
+    if r == 0 or v == 0:
+        return ConcertoPlan(u=0, patch_ids=torch.empty(0, dtype=torch.int64, device=dev),
+                            seg_start=torch.zeros(1, dtype=torch.int32, device=dev),
+                            pair_row=torch.empty(0, dtype=torch.int64, device=dev), rows=rows,
+                            slot=torch.empty(0, dtype=torch.int64, device=dev), n=n, views=v)
+    key = torch.empty(r * v + 1, dtype=torch.int64, device=dev)
+    lib.check(lib.ptv3_concerto_pair_keys(_p(corr), n, _p(rows), _p(scene), r, v, _p(img_base), img_base.shape[0],
+                                          int(patch_h), int(patch_w), int(n_patches), _p(key), _stream()),
+              "ptv3_concerto_pair_keys")
+    order = argsort_codes(key.view(1, -1), 63)[0][0].contiguous()
+    slot, seg_start, runs = pool_segments(key, order, 0)
+    u = runs - 1                                     # the last run is the one of the pairs without a patch
+    patch_ids = torch.empty(u, dtype=torch.int64, device=dev)
+    pair_row = torch.empty(r * v, dtype=torch.int64, device=dev)
+    lib.check(lib.ptv3_concerto_plan_finish(_p(key), _p(order), _p(seg_start), _p(rows), r, v, u, _p(patch_ids),
+                                            _p(pair_row), _stream()), "ptv3_concerto_plan_finish")
+    if check and u > 0 and int(patch_ids[-1].item()) >= n_patches:
+        raise RuntimeError(f"{who}: a correspondence points outside the {n_patches} patches of the batch's images")
+    return ConcertoPlan(u=u, patch_ids=patch_ids, seg_start=seg_start, pair_row=pair_row, rows=rows, slot=slot, n=n,
+                        views=v)
+
+
+def _concerto_plan_rows(who, plan, n):
+    if plan.n != n:
+        raise RuntimeError(f"{who}: the plan was made for {plan.n} feature rows, got {n}")
+    if plan.u == 0:
+        raise RuntimeError(f"{who}: no occupied patch (the caller's case, nothing to launch)")
+
+
+def concerto_patch_mean(feat, plan):
+    """mean (u, C) fp32: the mean of feat's rows over the pairs of every occupied patch, added in the plan's order in
+    fp32; feat (n, C) fp32 / bf16 is gathered by the kernel, no (pairs, C) copy exists."""
+    who = "concerto_patch_mean"
+    _chk(feat, f"{who}: feat", _F, 2)
+    n, c = feat.shape
+    _concerto_plan_rows(who, plan, n)
+    mean = torch.empty((plan.u, c), dtype=torch.float32, device=feat.device)
+    lib.check(lib.ptv3_concerto_patch_mean_fwd(_p(feat), _dt(feat), n, c, _p(plan.pair_row), _p(plan.seg_start), plan.u,
+                                               _p(mean), _stream()), "ptv3_concerto_patch_mean_fwd")
+    return mean
+
+
+def concerto_patch_mean_bwd(dmean, plan, dtype):
+    """dfeat (n, C) in `dtype`, every row written: sum over the row's pairs of dmean[slot] / count[slot], zeros for a row
+    without a pair."""
+    who = "concerto_patch_mean_bwd"
+    _chk(dmean, f"{who}: dmean", torch.float32, 2)
+    _concerto_plan_rows(who, plan, plan.n)
+    if dmean.shape[0] != plan.u or dtype not in _F:
+        raise RuntimeError(f"{who}: dmean {tuple(dmean.shape)} for {plan.u} patches, dtype {dtype}")
+    c = dmean.shape[1]
+    dfeat = torch.empty((plan.n, c), dtype=dtype, device=dmean.device)
+    lib.check(lib.ptv3_concerto_patch_mean_bwd(_p(dmean), _p(plan.rows), _p(plan.slot), _p(plan.seg_start), plan.n,
+                                               plan.rows.shape[0], plan.views, plan.u, c, _p(dfeat), _dt(dfeat),
+                                               _stream()), "ptv3_concerto_patch_mean_bwd")
+    return dfeat
+
+
+def concerto_cos_capable(d):
+    """D channels ptv3_concerto_cos_* cover: 1 <= D <= 2048."""
+    return bool(lib.ptv3_concerto_cos_capable(int(d)))
+
+
+def _concerto_cos_args(who, a, b, patch_ids):
+    _chk(a, f"{who}: a", _F, 2)
+    _chk(b, f"{who}: b", _F, 2)
+    _chk(patch_ids, f"{who}: patch_ids", torch.int64, 1)
+    if a.shape[1] != b.shape[1] or patch_ids.shape[0] != a.shape[0] or (b.shape[0] == 0 and a.shape[0] > 0):
+        raise RuntimeError(f"{who}: a {tuple(a.shape)} / b {tuple(b.shape)} / patch_ids {tuple(patch_ids.shape)}: "
+                           "expected (U, D), (patches, D) and (U)")
+
+
+def concerto_cos(a, b, patch_ids, shift=True):
+    """(loss (1), cos (U), stats (U, 4)), all fp32: loss = 10 mean_j (1 - cos(a[j], b[patch_ids[j]])), both rows less
+    their mean over D with `shift`, cos as torch.nn.CosineSimilarity(dim=1, eps=1e-6): each norm clamped from below.
+    stats = the two means and the two centred norms of every row, float64 sums rounded once."""
+    who = "concerto_cos"
+    _concerto_cos_args(who, a, b, patch_ids)
+    u, d = a.shape
+    if u == 0:
+        raise RuntimeError(f"{who}: no occupied patch (the caller's case, nothing to launch)")
+    dev = a.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    cos = torch.empty(u, dtype=torch.float32, device=dev)
+    stats = torch.empty((u, 4), dtype=torch.float32, device=dev)
+    lib.check(lib.ptv3_concerto_cos_fwd(_p(a), _dt(a), _p(b), _dt(b), _p(patch_ids), u, b.shape[0], d, int(bool(shift)),
+                                        _p(cos), _p(stats), _p(loss), _stream()), "ptv3_concerto_cos_fwd")
+    return loss, cos, stats
+
+
+def concerto_cos_bwd(dloss, a, b, patch_ids, shift=True):
+    """da (U, D) in a's dtype of dloss * concerto_cos(a, b, patch_ids, shift)[0]; the row statistics are formed again in
+    float64 by the kernel; b gets no gradient."""
+    who = "concerto_cos_bwd"
+    _concerto_cos_args(who, a, b, patch_ids)
+    _chk(dloss, f"{who}: dloss", torch.float32)
+    u, d = a.shape
+    if u == 0 or dloss.numel() != 1:
+        raise RuntimeError(f"{who}: dloss must hold one value, for U >= 1 rows")
+    da = torch.empty_like(a)
+    lib.check(lib.ptv3_concerto_cos_bwd(_p(dloss), _p(a), _dt(a), _p(b), _dt(b), _p(patch_ids), u, b.shape[0], d,
+                                        int(bool(shift)), _p(da), _stream()), "ptv3_concerto_cos_bwd")
+    return da
+
+
+# ---------------------------------------------------------------------------------------------
 # language-guided head of Point Prompt Training (csrc/ppt_head.hip)
 # ---------------------------------------------------------------------------------------------
 def ppt_head_capable(c, k):
