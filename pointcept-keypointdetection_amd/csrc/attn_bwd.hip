@@ -445,7 +445,7 @@ static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 using namespace ptv3;
 
 extern "C" size_t ptv3_window_attn_bwd_workspace_bytes(int64_t n, int64_t n_pad, int c, int heads, int dtype) {
-  const size_t esz = dtype == PTV3_F32 ? 4 : 2;
+  const size_t esz = dtype_bytes(dtype);
   return align256((size_t)n_pad * 3 * c * esz) + 2 * align256((size_t)n_pad * heads * sizeof(float)) +
          align256((size_t)n * sizeof(int32_t));
 }
@@ -469,7 +469,7 @@ int ptv3::window_attn_backward(WindowAttnCall& w, const WindowAttnSpec& spec) {
       return PTV3_ERR_LAUNCH;
     return PTV3_OK;
   }
-  const size_t esz = w.dtype == PTV3_F32 ? 4 : 2;
+  const size_t esz = dtype_bytes(w.dtype);
   char* ws = (char*)w.workspace;
   AttnBwdArgs a;
   a.qkv = w.qkv; a.out = w.out; a.dout = w.dout; a.win_order = w.win_order; a.win_inverse = w.win_inverse;
@@ -490,12 +490,11 @@ int ptv3::window_attn_backward(WindowAttnCall& w, const WindowAttnSpec& spec) {
     return (int)PTV3_OK;
   });
   const int64_t tot = n * (3 * c / 4);
-  if (w.dtype == PTV3_F32)
-    hipLaunchKernelGGL(unpad_add_kernel<float>, dim3((unsigned)cdiv(tot, 256)), dim3(256), 0, s, (const float*)a.dqkv_pad,
-                       w.win_inverse, dup, n, 3 * c, (float*)w.dqkv);
-  else
-    hipLaunchKernelGGL(unpad_add_kernel<__bf16>, dim3((unsigned)cdiv(tot, 256)), dim3(256), 0, s,
-                       (const __bf16*)a.dqkv_pad, w.win_inverse, dup, n, 3 * c, (__bf16*)w.dqkv);
+  by_dtype(w.dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(unpad_add_kernel<T>, dim3((unsigned)cdiv(tot, 256)), dim3(256), 0, s, (const T*)a.dqkv_pad,
+                       w.win_inverse, dup, n, 3 * c, (T*)w.dqkv);
+  });
   if (w.rpe_table) {
     const int ncol = 3 * (2 * w.pos_bnd + 1);
     hipLaunchKernelGGL(rpe_dtable_reduce_kernel, dim3((unsigned)cdiv((int64_t)ncol * heads, 256)), dim3(256), 0, s,

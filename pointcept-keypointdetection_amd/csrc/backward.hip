@@ -694,13 +694,17 @@ int tn_defer_flush(hipStream_t s) {
   const int prof = prof_begin(s, PROF_BACKWARD, q->flops, q->bytes, q->prof_nbr, q->prof_nbr ? q->prof_pairs : 0,
                               q->prof_nbr ? q->prof_pair_flops : 0.0);
   prof_kernel(prof, PK_GEMM_TN);
-#define TNG_LAUNCH(T, RB, LS)                                                                                       \
-  hipLaunchKernelGGL((gemm_tn_group_kernel<T, RB, LS>), dim3((unsigned)q->blocks), dim3(256), 2 * 64 * (LS) * sizeof(T), s, \
-                     q->grp, q->count)
-  if (q->dtype == PTV3_F32) TNG_LAUNCH(float, 64, 68);
-  else if (rbsel == 128) TNG_LAUNCH(__bf16, 128, 196);
-  else TNG_LAUNCH(__bf16, 64, 68);
-#undef TNG_LAUNCH
+  // 128 rows per block (PTV3_TN_RB = 128) exist in bf16 only
+  by_dtype(q->dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_value<64, 128>(q->dtype == PTV3_BF16 && rbsel == 128 ? 128 : 64, [&](auto RB) {
+      if constexpr (RB() == 64 || std::is_same_v<T, __bf16>) {
+        constexpr int LS = RB() == 128 ? 196 : 68;
+        hipLaunchKernelGGL((gemm_tn_group_kernel<T, RB(), LS>), dim3((unsigned)q->blocks), dim3(256),
+                           2 * 64 * LS * sizeof(T), s, q->grp, q->count);
+      }
+    });
+  });
   prof_end(prof, s);
   for (int k = 0; k < q->count; ++k)
     if (q->ns[k] > 1) {
@@ -763,7 +767,7 @@ extern "C" int ptv3_gemm_tn(const void* dy, const void* x, const int32_t* nbr, f
     q.blocks += (int)(grid.x * grid.y * grid.z);
     if (nbr && !q.prof_nbr) { q.prof_nbr = nbr; q.prof_pairs = m * kvol; q.prof_pair_flops = 2.0 * cin * cout; }
     else q.flops += 2.0 * m * cout * (double)cin * kvol;   // (a second convolution of a group would count dense)
-    q.bytes += ((double)m * (cout + cin)) * (dtype == PTV3_F32 ? 4 : 2) + (double)ns * nw * 4.0;
+    q.bytes += ((double)m * (cout + cin)) * dtype_bytes(dtype) + (double)ns * nw * 4.0;
     q.ns[q.count] = (int)ns; q.nw[q.count] = nw; q.dw[q.count] = dw; q.db[q.count] = dbias; q.ws[q.count] = (float*)workspace;
     ++q.count;
     return PTV3_OK;
@@ -771,26 +775,26 @@ extern "C" int ptv3_gemm_tn(const void* dy, const void* x, const int32_t* nbr, f
   // LDS: two [64][LS] operand blocks; the 64 x 64 fp32 cross-wave reduction reuses them after the last block
   static int rbsel = -1;
   if (rbsel < 0) { const char* e = getenv("PTV3_TN_RB"); rbsel = e ? atoi(e) : 64; }
-#define TN_LAUNCH(T, RB, LS)                                                                              \
-  do {                                                                                                    \
-    constexpr size_t lds = 2 * 64 * (LS) * sizeof(T);                                                     \
-    static_assert(lds >= 64 * 64 * sizeof(float) && lds <= 64 * 1024, "gemm_tn LDS");                     \
-    hipLaunchKernelGGL((gemm_tn_kernel<T, RB, LS>), grid, dim3(256), lds, s, a);                          \
-  } while (0)
   // weight gradient dW = dY^T gather(X): 2 m cout kvol cin flops dense (active pairs counted on the device for a
   // conv); reads dY once and X once (gathered), writes the fp32 gradient slabs
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
+  const int esz = dtype_bytes(dtype);
   const int prof = prof_begin(s, PROF_BACKWARD, 2.0 * m * cout * (double)kvol * cin,
                               ((double)m * (cout + cin)) * esz + (double)ns * nw * 4.0, nbr, nbr ? m * kvol : 0,
                               2.0 * cin * cout);
   prof_kernel(prof, PK_GEMM_TN);
-  if (dtype == PTV3_F32) {
-    TN_LAUNCH(float, 64, 68);
-  } else {
-    if (rbsel == 128) TN_LAUNCH(__bf16, 128, 196); else TN_LAUNCH(__bf16, 64, 68);
-  }
+  // 128 rows per block (PTV3_TN_RB = 128) exist in bf16 only
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_value<64, 128>(dtype == PTV3_BF16 && rbsel == 128 ? 128 : 64, [&](auto RB) {
+      if constexpr (RB() == 64 || std::is_same_v<T, __bf16>) {
+        constexpr int LS = RB() == 128 ? 196 : 68;
+        constexpr size_t lds = 2 * 64 * LS * sizeof(T);
+        static_assert(lds >= 64 * 64 * sizeof(float) && lds <= 64 * 1024, "gemm_tn LDS");
+        hipLaunchKernelGGL((gemm_tn_kernel<T, RB(), LS>), grid, dim3(256), lds, s, a);
+      }
+    });
+  });
   prof_end(prof, s);
-#undef TN_LAUNCH
   if (ns > 1) {
     if (dbias) slab_sum((const float*)workspace, (int)ns, nw + cout, dw, s, nw, dbias);
     else slab_sum((const float*)workspace, (int)ns, nw, dw, s);
@@ -823,15 +827,13 @@ extern "C" int ptv3_col_reduce(const void* a, const void* b, const float* mu, co
   const int64_t ns = col_chunks(m, &rb);
   PTV3_REQUIRE(workspace_bytes >= (size_t)ns * nq * c * sizeof(float), "col_reduce: workspace too small");
   dim3 grid((unsigned)ns, (unsigned)cdiv(c, 64));
-#define CR_LAUNCH(T, MODE)                                                                                     \
-  hipLaunchKernelGGL((col_reduce_kernel<T, MODE>), grid, dim3(256), 0, s, (const T*)a, (const T*)b, mu, rs, mu_scale, \
-                     m, c, rb, (float*)workspace)
-  if (dtype == PTV3_F32) {
-    if (mode == 0) CR_LAUNCH(float, 0); else if (mode == 1) CR_LAUNCH(float, 1); else if (mode == 2) CR_LAUNCH(float, 2); else CR_LAUNCH(float, 3);
-  } else {
-    if (mode == 0) CR_LAUNCH(__bf16, 0); else if (mode == 1) CR_LAUNCH(__bf16, 1); else if (mode == 2) CR_LAUNCH(__bf16, 2); else CR_LAUNCH(__bf16, 3);
-  }
-#undef CR_LAUNCH
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_value<0, 1, 2, 3>(mode, [&](auto MODE) {
+      hipLaunchKernelGGL((col_reduce_kernel<T, MODE()>), grid, dim3(256), 0, s, (const T*)a, (const T*)b, mu, rs,
+                         mu_scale, m, c, rb, (float*)workspace);
+    });
+  });
   slab_sum((const float*)workspace, (int)ns, (int64_t)nq * c, out, s);
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
@@ -852,21 +854,18 @@ extern "C" int ptv3_layernorm_bwd(const void* x, const void* dy, const void* add
   PTV3_REQUIRE(workspace_bytes >= (size_t)ns * 2 * c * sizeof(float), "layernorm_bwd: workspace too small");
   const int nc = (int)cdiv(c, 64);
   const bool packed = c >= 32 && c <= 256 && (c & (c - 1)) == 0;
-#define LNB_LAUNCH(T, NC)                                                                                      \
-  hipLaunchKernelGGL((layernorm_bwd_kernel<T, NC>), dim3((unsigned)ns), dim3(256), 0, s, (const T*)x, (const T*)dy, \
-                     (const T*)add, gamma, m, c, eps, rb, (T*)dx, (float*)workspace)
-#define LNB_CASE(T)                                                                                                \
-  if (packed)                                                                                                      \
-    hipLaunchKernelGGL((layernorm_bwd_packed_kernel<T>), dim3((unsigned)ns), dim3(256), 0, s, (const T*)x,         \
-                       (const T*)dy, (const T*)add, gamma, m, c, eps, rb, (T*)dx, (float*)workspace);              \
-  else if (nc <= 1) LNB_LAUNCH(T, 1);               \
-  else if (nc <= 2) LNB_LAUNCH(T, 2);               \
-  else if (nc <= 4) LNB_LAUNCH(T, 4);               \
-  else if (nc <= 8) LNB_LAUNCH(T, 8);               \
-  else LNB_LAUNCH(T, 16);
-  if (dtype == PTV3_F32) { LNB_CASE(float) } else { LNB_CASE(__bf16) }
-#undef LNB_CASE
-#undef LNB_LAUNCH
+  const int nc_pow2 = nc <= 1 ? 1 : nc <= 2 ? 2 : nc <= 4 ? 4 : nc <= 8 ? 8 : 16;   // 64-channel chunks per lane group
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (packed)
+      hipLaunchKernelGGL((layernorm_bwd_packed_kernel<T>), dim3((unsigned)ns), dim3(256), 0, s, (const T*)x,
+                         (const T*)dy, (const T*)add, gamma, m, c, eps, rb, (T*)dx, (float*)workspace);
+    else
+      by_value<1, 2, 4, 8, 16>(nc_pow2, [&](auto NC) {
+        hipLaunchKernelGGL((layernorm_bwd_kernel<T, NC()>), dim3((unsigned)ns), dim3(256), 0, s, (const T*)x,
+                           (const T*)dy, (const T*)add, gamma, m, c, eps, rb, (T*)dx, (float*)workspace);
+      });
+  });
   slab_sum((const float*)workspace, (int)ns, (int64_t)2 * c, dgamma_dbeta, s);
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
@@ -881,12 +880,11 @@ extern "C" int ptv3_act_bwd(const void* dy, const void* x, const float* scale, c
   const int64_t total4 = m * c / 4;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)cdiv(total4, 256));
-  if (dtype == PTV3_F32)
-    hipLaunchKernelGGL(act_bwd_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, (const float*)x, scale, shift,
-                       act, (float*)dx, total4, c);
-  else
-    hipLaunchKernelGGL(act_bwd_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)dy, (const __bf16*)x, scale,
-                       shift, act, (__bf16*)dx, total4, c);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(act_bwd_kernel<T>, grid, dim3(256), 0, s, (const T*)dy, (const T*)x, scale, shift, act, (T*)dx,
+                       total4, c);
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }
@@ -899,12 +897,10 @@ extern "C" int ptv3_affine2(const void* dy, const void* x, const float* ca, cons
   const int64_t total4 = m * c / 4;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)cdiv(total4, 256));
-  if (dtype == PTV3_F32)
-    hipLaunchKernelGGL(affine2_kernel<float>, grid, dim3(256), 0, s, (const float*)dy, (const float*)x, ca, cb, cc,
-                       (float*)dx, total4, c);
-  else
-    hipLaunchKernelGGL(affine2_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)dy, (const __bf16*)x, ca, cb, cc,
-                       (__bf16*)dx, total4, c);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(affine2_kernel<T>, grid, dim3(256), 0, s, (const T*)dy, (const T*)x, ca, cb, cc, (T*)dx, total4, c);
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }
@@ -915,12 +911,11 @@ extern "C" int ptv3_pool_max_bwd(const void* feat, const void* dy, const int64_t
   if (n_out == 0) return PTV3_OK;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)cdiv(n_out * c, 256));
-  if (dtype == PTV3_F32)
-    hipLaunchKernelGGL((segment_bwd_kernel<float, true>), grid, dim3(256), 0, s, (const float*)feat, (const float*)dy,
-                       order0, seg_start, n_out, c, (float*)dfeat);
-  else
-    hipLaunchKernelGGL((segment_bwd_kernel<__bf16, true>), grid, dim3(256), 0, s, (const __bf16*)feat,
-                       (const __bf16*)dy, order0, seg_start, n_out, c, (__bf16*)dfeat);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((segment_bwd_kernel<T, true>), grid, dim3(256), 0, s, (const T*)feat, (const T*)dy, order0,
+                       seg_start, n_out, c, (T*)dfeat);
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }
@@ -931,12 +926,11 @@ extern "C" int ptv3_segment_sum(const void* dy, const int64_t* order0, const int
   if (n_out == 0) return PTV3_OK;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)cdiv(n_out * c, 256));
-  if (dtype == PTV3_F32)
-    hipLaunchKernelGGL((segment_bwd_kernel<float, false>), grid, dim3(256), 0, s, (const float*)nullptr,
-                       (const float*)dy, order0, seg_start, n_out, c, (float*)out);
-  else
-    hipLaunchKernelGGL((segment_bwd_kernel<__bf16, false>), grid, dim3(256), 0, s, (const __bf16*)nullptr,
-                       (const __bf16*)dy, order0, seg_start, n_out, c, (__bf16*)out);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((segment_bwd_kernel<T, false>), grid, dim3(256), 0, s, (const T*)nullptr, (const T*)dy, order0,
+                       seg_start, n_out, c, (T*)out);
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }

@@ -719,30 +719,6 @@ static void launch_tail(const TailArgs& a, int c, hipStream_t s) {
   }
 }
 
-#define TAIL_LAUNCH(ARGS)                                                                                \
-  {                                                                                                      \
-    const int rt = row_tiles(m);                                                                         \
-    if (dtype == PTV3_F32) {                                                                             \
-      if (c == 32) { if (rt == 2) launch_tail<float, 2, 2>(ARGS, c, s); else launch_tail<float, 2, 1>(ARGS, c, s); } \
-      else { if (rt == 2) launch_tail<float, 4, 2>(ARGS, c, s); else launch_tail<float, 4, 1>(ARGS, c, s); }         \
-    } else {                                                                                             \
-      if (c == 32) { if (rt == 2) launch_tail<__bf16, 2, 2>(ARGS, c, s); else launch_tail<__bf16, 2, 1>(ARGS, c, s); } \
-      else { if (rt == 2) launch_tail<__bf16, 4, 2>(ARGS, c, s); else launch_tail<__bf16, 4, 1>(ARGS, c, s); }         \
-    }                                                                                                    \
-  }
-
-#define FUSED_LAUNCH(KERNEL, ARGS)                                                                     \
-  {                                                                                                    \
-    dim3 grid((unsigned)cdiv(m, 64)), block(256);                                                      \
-    if (dtype == PTV3_F32) {                                                                           \
-      if (c == 32) hipLaunchKernelGGL((KERNEL<float, 2>), grid, block, 0, s, ARGS);                    \
-      else hipLaunchKernelGGL((KERNEL<float, 4>), grid, block, 0, s, ARGS);                            \
-    } else {                                                                                           \
-      if (c == 32) hipLaunchKernelGGL((KERNEL<__bf16, 2>), grid, block, 0, s, ARGS);                   \
-      else hipLaunchKernelGGL((KERNEL<__bf16, 4>), grid, block, 0, s, ARGS);                           \
-    }                                                                                                  \
-  }
-
 // 0: not fusable, 1: wave-local register chain (C in {32,64}; bf16 wants chain-permuted weights),
 // 2: workgroup-cooperative (C in {128,256,512}; natural weights)
 static size_t coop_head_lds(int c, int esz) { return (size_t)16 * (c + 16 / esz) * esz; }
@@ -770,7 +746,7 @@ static int64_t coop_max_rows(int c) {
 // 3: the weight-streaming variant of block_wide.hip (its buffer stores address rows with 32-bit byte offsets)
 static bool wide_rows(int c, int hidden, int dtype, int64_t m) {
   return wide_capable(c, hidden, dtype) && m >= wide_min_rows(c) &&
-         m * 3 * c * (dtype == PTV3_F32 ? 4 : 2) < ((int64_t)1 << 31) - (1 << 20);
+         m * 3 * c * dtype_bytes(dtype) < ((int64_t)1 << 31) - (1 << 20);
 }
 
 extern "C" int ptv3_block_fusable(int c, int hidden, int dtype, int64_t m) {
@@ -778,7 +754,7 @@ extern "C" int ptv3_block_fusable(int c, int hidden, int dtype, int64_t m) {
   if (c == 32 || c == 64) return 1;
   if (wide_rows(c, hidden, dtype, m)) return 3;
   if ((c == 128 || c == 256 || c == 512) && hidden == 4 * c && m <= coop_max_rows(c) &&
-      coop_tail_lds(c, hidden, dtype == PTV3_F32 ? 4 : 2) <= 160 * 1024)
+      coop_tail_lds(c, hidden, dtype_bytes(dtype)) <= 160 * 1024)
     return 2;
   return 0;
 }
@@ -794,17 +770,6 @@ static void launch_tail_coop(const TailArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((block_tail_coop_kernel<T, C, 4>), dim3((unsigned)cdiv(a.m, 16)), dim3(64 * Coop<C>::NW),
                      coop_tail_lds(C, 4 * C, sizeof(T)), s, a);
 }
-#define COOP_LAUNCH(FN, ARGS)                                              \
-  if (dtype == PTV3_F32) {                                                 \
-    if (c == 128) FN<float, 128>(ARGS, s);                                 \
-    else if (c == 256) FN<float, 256>(ARGS, s);                            \
-    else FN<float, 512>(ARGS, s);                                          \
-  } else {                                                                 \
-    if (c == 128) FN<__bf16, 128>(ARGS, s);                                \
-    else if (c == 256) FN<__bf16, 256>(ARGS, s);                           \
-    else FN<__bf16, 512>(ARGS, s);                                         \
-  }
-
 extern "C" int ptv3_mlp2_fusable(int cin, int hidden, int cout, int dtype) {
   return (cin == 32 || cin == 64) && hidden > 0 && hidden % 64 == 0 && cout > 0 && cout % 4 == 0 && cout <= 64 &&
          (dtype == PTV3_F32 || dtype == PTV3_BF16);
@@ -821,7 +786,7 @@ extern "C" int ptv3_mlp2(const void* x, const void* w1, const float* b1, const f
   Mlp2Args a;
   a.x = x; a.w1 = w1; a.b1 = b1; a.s1 = s1; a.t1 = t1; a.w2 = w2; a.b2 = b2; a.out = out;
   a.m = m; a.hidden = hidden; a.cout = cout; a.act = act; a.out_f32 = out_f32;
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
+  const int esz = dtype_bytes(dtype);
   const int prof = prof_begin(s, PROF_LINEAR, 2.0 * m * hidden * (cin + cout),
                               ((double)m * cin + (double)hidden * (cin + cout)) * esz + (double)m * cout * (out_f32 ? 4 : esz),
                               nullptr, 0, 0.0);
@@ -832,28 +797,22 @@ extern "C" int ptv3_mlp2(const void* x, const void* w1, const float* b1, const f
   const bool wlds = wb <= 128 * 1024;
   const int64_t nblocks = cdiv(m, 64 * rt);
   dim3 grid((unsigned)(wlds ? std::min<int64_t>(nblocks, 2 * 256) : nblocks)), block(256);
-#define MLP2_GO(KERNEL_T, KERNEL_F)                                                               \
-  if (wlds) {                                                                                     \
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&KERNEL_T), 128 * 1024);                     \
-    hipLaunchKernelGGL(KERNEL_T, grid, block, wb, s, a);                                          \
-  } else {                                                                                        \
-    hipLaunchKernelGGL(KERNEL_F, grid, block, 0, s, a);                                           \
-  }
-#define MLP2_RT(T, NTI, NTO)                                                                      \
-  if (rt == 2) { MLP2_GO((mlp2_kernel<T, NTI, NTO, 2, true>), (mlp2_kernel<T, NTI, NTO, 2, false>)) } \
-  else { MLP2_GO((mlp2_kernel<T, NTI, NTO, 1, true>), (mlp2_kernel<T, NTI, NTO, 1, false>)) }
-#define MLP2_CASE(T, NTI)                                                                         \
-  if (nto == 1) { MLP2_RT(T, NTI, 1) }                                                            \
-  else if (nto == 2) { MLP2_RT(T, NTI, 2) }                                                       \
-  else { MLP2_RT(T, NTI, 4) }
-  if (dtype == PTV3_F32) {
-    if (cin == 32) { MLP2_CASE(float, 2) } else { MLP2_CASE(float, 4) }
-  } else {
-    if (cin == 32) { MLP2_CASE(__bf16, 2) } else { MLP2_CASE(__bf16, 4) }
-  }
-#undef MLP2_CASE
-#undef MLP2_RT
-#undef MLP2_GO
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_value<32, 64>(cin, [&](auto CIN) {
+      by_value<1, 2, 4>(nto, [&](auto NTO) {
+        by_value<1, 2>(rt, [&](auto RT) {
+          constexpr int NTI = CIN() / 16;
+          if (wlds) {
+            ensure_dynamic_lds(reinterpret_cast<const void*>(&mlp2_kernel<T, NTI, NTO(), RT(), true>), 128 * 1024);
+            hipLaunchKernelGGL((mlp2_kernel<T, NTI, NTO(), RT(), true>), grid, block, wb, s, a);
+          } else {
+            hipLaunchKernelGGL((mlp2_kernel<T, NTI, NTO(), RT(), false>), grid, block, 0, s, a);
+          }
+        });
+      });
+    });
+  });
   prof_end(prof, s);
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
@@ -875,7 +834,7 @@ extern "C" int ptv3_block_head(const void* x, const float* slab, int splits, con
   if (m == 0) return PTV3_OK;
   hipStream_t s = (hipStream_t)stream;
   HeadArgs a{x, slab, splits, conv_bias, shortcut, g0, b0, g1, b1, wqkv, bqkv, f1, qkv, m, eps};
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
+  const int esz = dtype_bytes(dtype);
   const int prof = prof_begin(s, PROF_LINEAR, 2.0 * m * c * 3 * c, ((double)m * c * 6 + 3.0 * c * c) * esz, nullptr, 0, 0.0);
   prof_kernel(prof, mode == 1 ? PK_BLOCK_HEAD : mode == 3 ? PK_BLOCK_HEAD_WIDE : PK_BLOCK_HEAD_COOP);
   if (mode == 3) {
@@ -884,15 +843,17 @@ extern "C" int ptv3_block_head(const void* x, const float* slab, int splits, con
     const int64_t nblocks = cdiv(m, 64);
     const size_t wb = (size_t)3 * c * (c + 16 / esz) * esz + (size_t)8 * c * sizeof(float);  // weights + vectors
     const dim3 grid_l((unsigned)std::min<int64_t>(nblocks, 4 * 256)), block(256);
-    if (dtype == PTV3_F32) {
-      if (c == 32) hipLaunchKernelGGL((block_head_kernel<float, 2, true>), grid_l, block, wb, s, a);
-      else hipLaunchKernelGGL((block_head_kernel<float, 4, true>), grid_l, block, wb, s, a);
-    } else {
-      if (c == 32) hipLaunchKernelGGL((block_head_kernel<__bf16, 2, true>), grid_l, block, wb, s, a);
-      else hipLaunchKernelGGL((block_head_kernel<__bf16, 4, true>), grid_l, block, wb, s, a);
-    }
+    by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      by_value<32, 64>(c, [&](auto C) {
+        hipLaunchKernelGGL((block_head_kernel<T, C() / 16, true>), grid_l, block, wb, s, a);
+      });
+    });
   } else {
-    COOP_LAUNCH(launch_head_coop, a)
+    by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      by_value<128, 256, 512>(c, [&](auto C) { launch_head_coop<T, C()>(a, s); });
+    });
   }
   prof_end(prof, s);
   PTV3_LAUNCH_CHECK();
@@ -909,16 +870,24 @@ extern "C" int ptv3_block_tail(const void* attn, const void* f1, const void* wpr
   if (m == 0) return PTV3_OK;
   hipStream_t s = (hipStream_t)stream;
   TailArgs a{attn, f1, wproj, bproj, g2, b2, w1, bias1, w2, bias2, out, m, hidden, eps};
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
+  const int esz = dtype_bytes(dtype);
   const int prof = prof_begin(s, PROF_LINEAR, 2.0 * m * c * (c + 2.0 * hidden),
                               ((double)m * c * 3 + (double)c * c + 2.0 * c * hidden) * esz, nullptr, 0, 0.0);
   prof_kernel(prof, mode == 1 ? PK_BLOCK_TAIL : mode == 3 ? PK_BLOCK_TAIL_WIDE : PK_BLOCK_TAIL_COOP);
   if (mode == 3) {
     launch_block_tail_wide(a, c, dtype, s);
   } else if (mode == 1) {
-    TAIL_LAUNCH(a)
+    by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      by_value<32, 64>(c, [&](auto C) {
+        by_value<1, 2>(row_tiles(m), [&](auto RT) { launch_tail<T, C() / 16, RT()>(a, c, s); });
+      });
+    });
   } else {
-    COOP_LAUNCH(launch_tail_coop, a)
+    by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      by_value<128, 256, 512>(c, [&](auto C) { launch_tail_coop<T, C()>(a, s); });
+    });
   }
   prof_end(prof, s);
   PTV3_LAUNCH_CHECK();

@@ -46,12 +46,11 @@ static int rowscale_add(const void* x, const float* u, float keep, const void* s
   const int64_t total4 = m * c / 4;
   if (total4 == 0) return PTV3_OK;
   dim3 grid((unsigned)cdiv(total4, 256));
-  if (dtype == PTV3_F32)
-    hipLaunchKernelGGL(rowscale_add_kernel<float>, grid, dim3(256), 0, s, (const float*)x, u, keep, inv_keep,
-                       (const float*)skip, (float*)out, total4, c / 4);
-  else
-    hipLaunchKernelGGL(rowscale_add_kernel<__bf16>, grid, dim3(256), 0, s, (const __bf16*)x, u, keep, inv_keep,
-                       (const __bf16*)skip, (__bf16*)out, total4, c / 4);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(rowscale_add_kernel<T>, grid, dim3(256), 0, s, (const T*)x, u, keep, inv_keep, (const T*)skip,
+                       (T*)out, total4, c / 4);
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }
@@ -68,7 +67,7 @@ struct Bump {   // 256-byte aligned carving of the caller's workspace
   }
 };
 
-static size_t esize(int dtype) { return dtype == PTV3_F32 ? 4 : 2; }
+static size_t esize(int dtype) { return dtype_bytes(dtype); }
 
 // scratch shared by every op of a call (each op has finished with it when the next one starts: one stream)
 static size_t op_scratch_bytes(const ptv3_block_train* b, bool backward) {
@@ -96,7 +95,7 @@ static size_t op_scratch_bytes(const ptv3_block_train* b, bool backward) {
 static int check_block(const ptv3_block_train* b, const char* what) {
   PTV3_REQUIRE(b != nullptr, "%s: NULL descriptor", what);
   PTV3_REQUIRE(b->dtype == PTV3_F32 || b->dtype == PTV3_BF16, "%s: dtype %d", what, b->dtype);
-  const int gran = b->dtype == PTV3_F32 ? 4 : 8;
+  const int gran = dtype_granule(b->dtype);
   PTV3_REQUIRE(b->n >= 0 && b->c > 0 && b->hidden > 0 && b->c % gran == 0 && b->hidden % gran == 0,
                "%s: n=%lld c=%d hidden=%d (channels in multiples of %d)", what, (long long)b->n, b->c, b->hidden, gran);
   PTV3_REQUIRE(b->heads > 0 && b->c % b->heads == 0, "%s: %d heads for %d channels", what, b->heads, b->c);

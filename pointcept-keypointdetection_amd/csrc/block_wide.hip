@@ -1008,35 +1008,39 @@ static bool two_wgs() {
   if (v < 0) { const char* e = getenv("PTV3_WIDE_WGS"); v = (e && atoi(e) == 1) ? 0 : 1; }
   return v == 1;
 }
-void launch_block_head_wide(const HeadArgs& a, int c, int dtype, hipStream_t s) {
+// (dtype, c) -> f(TypeTag<T>, NT, RT, NBUF, WGS), the last four as integral constants: RT row tiles per wave (1 in fp32,
+// 2 in bf16), a ring of 3 units or the deep one (6 at C = 128, 4 at C = 256); two workgroups per CU exist in bf16 at
+// C = 128 with the ring of 3 only
+template <typename F>
+static void by_wide_shape(int c, int dtype, F&& f) {
   const bool deep = deep_ring();
-  if (dtype == PTV3_F32) {
-    if (c == 128) { if (deep) launch_head_wide<float, 8, 1, 6>(a, s); else launch_head_wide<float, 8, 1, 3>(a, s); }
-    else { if (deep) launch_head_wide<float, 16, 1, 4>(a, s); else launch_head_wide<float, 16, 1, 3>(a, s); }
-  } else {
-    if (c == 128) {
-      if (deep) launch_head_wide<__bf16, 8, 2, 6>(a, s);
-      else if (two_wgs()) launch_head_wide<__bf16, 8, 2, 3, 2>(a, s);
-      else launch_head_wide<__bf16, 8, 2, 3>(a, s);
-    }
-    else { if (deep) launch_head_wide<__bf16, 16, 2, 4>(a, s); else launch_head_wide<__bf16, 16, 2, 3>(a, s); }
-  }
+  const int wgs = dtype == PTV3_BF16 && c == 128 && !deep && two_wgs() ? 2 : 1;
+  by_dtype(dtype, [&](auto t) {
+    constexpr bool bf16 = std::is_same_v<typename decltype(t)::type, __bf16>;
+    by_value<128, 256>(c, [&](auto C) {
+      by_value<0, 1>(deep, [&](auto DEEP) {
+        by_value<1, 2>(wgs, [&](auto WGS) {
+          if constexpr (WGS() == 1 || (bf16 && C() == 128 && !DEEP())) {
+            constexpr int NBUF = !DEEP() ? 3 : C() == 128 ? 6 : 4;
+            f(t, std::integral_constant<int, C() / 16>{}, std::integral_constant<int, bf16 ? 2 : 1>{},
+              std::integral_constant<int, NBUF>{}, WGS);
+          }
+        });
+      });
+    });
+  });
+}
+void launch_block_head_wide(const HeadArgs& a, int c, int dtype, hipStream_t s) {
+  by_wide_shape(c, dtype, [&](auto t, auto NT, auto RT, auto NBUF, auto WGS) {
+    launch_head_wide<typename decltype(t)::type, NT(), RT(), NBUF(), WGS()>(a, s);
+  });
 }
 void launch_block_tail_wide(const TailArgs& a0, int c, int dtype, hipStream_t s) {
-  const bool deep = deep_ring();
   TailArgs a = a0;
   if (const char* e = getenv("PTV3_WIDE_ABLATE")) a.ablate = atoi(e);
-  if (dtype == PTV3_F32) {
-    if (c == 128) { if (deep) launch_tail_wide<float, 8, 1, 6>(a, s); else launch_tail_wide<float, 8, 1, 3>(a, s); }
-    else { if (deep) launch_tail_wide<float, 16, 1, 4>(a, s); else launch_tail_wide<float, 16, 1, 3>(a, s); }
-  } else {
-    if (c == 128) {
-      if (deep) launch_tail_wide<__bf16, 8, 2, 6>(a, s);
-      else if (two_wgs()) launch_tail_wide<__bf16, 8, 2, 3, 2>(a, s);
-      else launch_tail_wide<__bf16, 8, 2, 3>(a, s);
-    }
-    else { if (deep) launch_tail_wide<__bf16, 16, 2, 4>(a, s); else launch_tail_wide<__bf16, 16, 2, 3>(a, s); }
-  }
+  by_wide_shape(c, dtype, [&](auto t, auto NT, auto RT, auto NBUF, auto WGS) {
+    launch_tail_wide<typename decltype(t)::type, NT(), RT(), NBUF(), WGS()>(a, s);
+  });
 }
 
 // ---- ptv3_block_tail_sliced: capability, policy and launch
@@ -1102,14 +1106,14 @@ static void launch_tail_sliced(const TailArgs& a, int groups, float* ws, hipStre
   const int64_t n8 = a.m * C / 8, stride = a.m * C * (int64_t)sizeof(float);
   const dim3 fgrid((unsigned)cdiv(n8, 256));
   __bf16* out = reinterpret_cast<__bf16*>(a.out);
-  if (groups == 2) hipLaunchKernelGGL(tail_sliced_finish_kernel<2>, fgrid, dim3(256), 0, s, ws, groups, n8, stride, out);
-  else if (groups == 4) hipLaunchKernelGGL(tail_sliced_finish_kernel<4>, fgrid, dim3(256), 0, s, ws, groups, n8, stride, out);
-  else hipLaunchKernelGGL(tail_sliced_finish_kernel<8>, fgrid, dim3(256), 0, s, ws, groups, n8, stride, out);
+  by_value<2, 4, 8>(groups == 2 || groups == 4 ? groups : 8, [&](auto B) {   // slabs summed per batch
+    hipLaunchKernelGGL(tail_sliced_finish_kernel<B()>, fgrid, dim3(256), 0, s, ws, groups, n8, stride, out);
+  });
 }
 
 // ---- ptv3_rows_linear: capability and launch
 static int rows_hslr(int c, int dtype) {
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
+  const int esz = dtype_bytes(dtype);
   int h = 64;
   while (h > 16 && h * c * esz > 32 * 1024) h >>= 1;
   return h;
@@ -1118,7 +1122,7 @@ bool rows_linear_capable(int c, int cout, int dtype, int64_t m) {
   if (!(c == 128 || c == 256 || c == 512) || (dtype != PTV3_F32 && dtype != PTV3_BF16)) return false;
   const int h = rows_hslr(c, dtype);
   if (h < 32 || cout % h != 0 || cout > 8192) return false;     // fp32 at c = 512: a 32-row unit would be 64 KB
-  return m * (int64_t)std::max(cout, c) * (dtype == PTV3_F32 ? 4 : 2) < ((int64_t)1 << 31) - (1 << 20);
+  return m * (int64_t)std::max(cout, c) * dtype_bytes(dtype) < ((int64_t)1 << 31) - (1 << 20);
 }
 
 template <typename T, int NT, int RT, int HSLR, int PRO>
@@ -1138,19 +1142,18 @@ static void launch_rows_pro(const RowsLinArgs& a, hipStream_t s) {
 template <typename T, int NT, int RT, int HSLR>
 static void launch_rows(const RowsLinArgs& a, int pro, hipStream_t s) {
   constexpr int RTP = (NT >= 32) ? 1 : RT;
-  if (pro == 2) launch_rows_pro<T, NT, RTP, HSLR, 2>(a, s);
-  else if (pro == 1) launch_rows_pro<T, NT, RTP, HSLR, 1>(a, s);
-  else launch_rows_pro<T, NT, RT, HSLR, 0>(a, s);
+  by_value<0, 1, 2>(pro, [&](auto PRO) { launch_rows_pro<T, NT, PRO() == 0 ? RT : RTP, HSLR, PRO()>(a, s); });
 }
 
 void launch_rows_linear(const RowsLinArgs& a, int c, int pro, int dtype, hipStream_t s) {
-  if (dtype == PTV3_F32) {
-    if (c == 128) launch_rows<float, 8, 1, 32>(a, pro, s); else launch_rows<float, 16, 1, 32>(a, pro, s);
-  } else {
-    if (c == 128) launch_rows<__bf16, 8, 2, 64>(a, pro, s);
-    else if (c == 256) launch_rows<__bf16, 16, 2, 64>(a, pro, s);
-    else launch_rows<__bf16, 32, 2, 32>(a, pro, s);
-  }
+  // a unit of HSLR weight rows is 32 KB at most; fp32 has no C = 512 (rows_linear_capable)
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_value<128, 256, 512>(c, [&](auto C) {
+      constexpr bool bf16 = std::is_same_v<T, __bf16>;
+      if constexpr (bf16 || C() <= 256) launch_rows<T, C() / 16, bf16 ? 2 : 1, bf16 && C() <= 256 ? 64 : 32>(a, pro, s);
+    });
+  });
 }
 
 }  // namespace ptv3
@@ -1195,8 +1198,7 @@ extern "C" int ptv3_block_tail_sliced(const void* attn, const void* f1, const vo
                                   (groups > 1 ? 2.0 * need : 0.0),
                               nullptr, 0, 0.0);
   prof_kernel(prof, PK_BLOCK_TAIL_SLICED);
-  if (c == 128) launch_tail_sliced<8, SLICED_RT>(a, groups, (float*)workspace, s);
-  else launch_tail_sliced<16, SLICED_RT>(a, groups, (float*)workspace, s);
+  by_value<128, 256>(c, [&](auto C) { launch_tail_sliced<C() / 16, SLICED_RT>(a, groups, (float*)workspace, s); });
   prof_end(prof, s);
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
@@ -1218,7 +1220,7 @@ extern "C" int ptv3_rows_linear(const void* x, const void* shortcut, const float
   if (m == 0) return PTV3_OK;
   hipStream_t s = (hipStream_t)stream;
   const RowsLinArgs a{x, shortcut, g0, b0, g1, b1, w, bias, res, f1, out, m, cout, act, eps};
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
+  const int esz = dtype_bytes(dtype);
   const int prof = prof_begin(s, PROF_LINEAR, 2.0 * m * c * (double)cout,
                               ((double)m * c * (1 + 2 * (pro == 2)) + (double)c * cout + (double)m * cout * (1 + (res != nullptr))) * esz,
                               nullptr, 0, 0.0);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <mutex>
+#include <type_traits>
 
 #include "../../include/ptv3_hip.h"   // PTV3_OK / PTV3_ERR_*, PTV3_F32 / PTV3_BF16
 
@@ -15,6 +16,23 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Host-side dispatch: an entry point turns its run-time dtype code and widths into template arguments here.
+//   by_dtype(dtype, [&](auto t) { using T = typename decltype(t)::type;
+//     by_value<32, 64>(c, [&](auto C) { launch<T, C()>(...); }); });
+// Both return false, and call nothing, for a value outside the list: what a ladder instantiates is what its lists
+// name.  A pair that has no kernel is cut out inside the lambda with `if constexpr`.
+template <typename T> struct TypeTag { using type = T; };
+template <typename F> inline bool by_dtype(int dtype, F&& f) {
+  if (dtype == PTV3_F32) { f(TypeTag<float>{}); return true; }
+  if (dtype == PTV3_BF16) { f(TypeTag<__bf16>{}); return true; }
+  return false;
+}
+template <int... Vs, typename F> inline bool by_value(int v, F&& f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+inline int dtype_bytes(int dtype) { return dtype == PTV3_F32 ? 4 : 2; }     // element size
+inline int dtype_granule(int dtype) { return dtype == PTV3_F32 ? 4 : 8; }   // elements in 16 bytes of K
 
 // 4 contiguous elements of T as one register group
 template <typename T> struct Vec4;

@@ -343,11 +343,6 @@ extern "C" int ptv3_concerto_plan_finish(const int64_t* key, const int64_t* orde
   return PTV3_OK;
 }
 
-#define CC_BY_T(dtype, LAUNCH) \
-  do {                         \
-    if ((dtype) == PTV3_BF16) { LAUNCH(__bf16); } else { LAUNCH(float); } \
-  } while (0)
-
 extern "C" int ptv3_concerto_patch_mean_fwd(const void* feat, int dtype, int64_t n, int C, const int64_t* pair_row,
                                             const int32_t* seg_start, int64_t U, float* mean, void* stream) {
   PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "concerto_patch_mean_fwd: feat must be fp32 or bf16");
@@ -357,15 +352,13 @@ extern "C" int ptv3_concerto_patch_mean_fwd(const void* feat, int dtype, int64_t
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)cdiv(U, CC_WAVES));
   const bool vec = C % 4 == 0 && cc_aligned16(feat) && cc_aligned16(mean);
-#define CC_FWD(T)                                                                                                     \
-  if (vec)                                                                                                            \
-    hipLaunchKernelGGL((cc_mean_fwd_kernel<T, 4>), grid, dim3(CC_THREADS), 0, st, (const T*)feat, n, C, pair_row,     \
-                       seg_start, U, mean);                                                                           \
-  else                                                                                                                \
-    hipLaunchKernelGGL((cc_mean_fwd_kernel<T, 1>), grid, dim3(CC_THREADS), 0, st, (const T*)feat, n, C, pair_row,     \
-                       seg_start, U, mean)
-  CC_BY_T(dtype, CC_FWD);
-#undef CC_FWD
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_value<1, 4>(vec ? 4 : 1, [&](auto VEC) {
+      hipLaunchKernelGGL((cc_mean_fwd_kernel<T, VEC()>), grid, dim3(CC_THREADS), 0, st, (const T*)feat, n, C, pair_row,
+                         seg_start, U, mean);
+    });
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }
@@ -381,15 +374,13 @@ extern "C" int ptv3_concerto_patch_mean_bwd(const float* dmean, const int64_t* r
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)cdiv(n, CC_WAVES));
   const bool vec = C % 4 == 0 && cc_aligned16(dmean) && cc_aligned16(dfeat);
-#define CC_BWD(T)                                                                                                     \
-  if (vec)                                                                                                            \
-    hipLaunchKernelGGL((cc_mean_bwd_kernel<T, 4>), grid, dim3(CC_THREADS), 0, st, dmean, rows, slot, seg_start, n, R, \
-                       V, U, C, (T*)dfeat);                                                                           \
-  else                                                                                                                \
-    hipLaunchKernelGGL((cc_mean_bwd_kernel<T, 1>), grid, dim3(CC_THREADS), 0, st, dmean, rows, slot, seg_start, n, R, \
-                       V, U, C, (T*)dfeat)
-  CC_BY_T(dtype, CC_BWD);
-#undef CC_BWD
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_value<1, 4>(vec ? 4 : 1, [&](auto VEC) {
+      hipLaunchKernelGGL((cc_mean_bwd_kernel<T, VEC()>), grid, dim3(CC_THREADS), 0, st, dmean, rows, slot, seg_start, n,
+                         R, V, U, C, (T*)dfeat);
+    });
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }
@@ -397,13 +388,7 @@ extern "C" int ptv3_concerto_patch_mean_bwd(const float* dmean, const int64_t* r
 extern "C" int ptv3_concerto_cos_capable(int D) { return D >= 1 && D <= CC_MAX_D; }
 
 // entries per lane: 2 (D <= 128), 8 (<= 512), 24 (<= 1536), 32 (<= 2048)
-#define CC_BY_D(D, LAUNCH)         \
-  do {                             \
-    if ((D) <= 128) { LAUNCH(2); } \
-    else if ((D) <= 512) { LAUNCH(8); } \
-    else if ((D) <= 1536) { LAUNCH(24); } \
-    else { LAUNCH(32); }           \
-  } while (0)
+static int cc_dpl(int D) { return D <= 128 ? 2 : D <= 512 ? 8 : D <= 1536 ? 24 : 32; }
 
 static int cc_cos_args(const char* who, int a_dtype, int b_dtype, int64_t U, int64_t nb, int D) {
   PTV3_REQUIRE(ptv3_concerto_cos_capable(D), "%s: D=%d unsupported (1 to %d channels)", who, D, CC_MAX_D);
@@ -422,21 +407,16 @@ extern "C" int ptv3_concerto_cos_fwd(const void* a, int a_dtype, const void* b, 
   PTV3_REQUIRE(a && b && patch_ids && cosv && stats && loss, "concerto_cos_fwd: a pointer is NULL");
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)cdiv(U, CC_WAVES));
-#define CC_COS(DPL)                                                                                                   \
-  if (a_dtype == PTV3_BF16 && b_dtype == PTV3_BF16)                                                                   \
-    hipLaunchKernelGGL((cc_cos_fwd_kernel<__bf16, __bf16, DPL>), grid, dim3(CC_THREADS), 0, st, (const __bf16*)a,     \
-                       (const __bf16*)b, patch_ids, U, nb, D, shift, cosv, stats);                                    \
-  else if (a_dtype == PTV3_BF16)                                                                                      \
-    hipLaunchKernelGGL((cc_cos_fwd_kernel<__bf16, float, DPL>), grid, dim3(CC_THREADS), 0, st, (const __bf16*)a,      \
-                       (const float*)b, patch_ids, U, nb, D, shift, cosv, stats);                                     \
-  else if (b_dtype == PTV3_BF16)                                                                                      \
-    hipLaunchKernelGGL((cc_cos_fwd_kernel<float, __bf16, DPL>), grid, dim3(CC_THREADS), 0, st, (const float*)a,       \
-                       (const __bf16*)b, patch_ids, U, nb, D, shift, cosv, stats);                                    \
-  else                                                                                                                \
-    hipLaunchKernelGGL((cc_cos_fwd_kernel<float, float, DPL>), grid, dim3(CC_THREADS), 0, st, (const float*)a,        \
-                       (const float*)b, patch_ids, U, nb, D, shift, cosv, stats)
-  CC_BY_D(D, CC_COS);
-#undef CC_COS
+  by_dtype(a_dtype, [&](auto ta) {
+    using A = typename decltype(ta)::type;
+    by_dtype(b_dtype, [&](auto tb) {
+      using B = typename decltype(tb)::type;
+      by_value<2, 8, 24, 32>(cc_dpl(D), [&](auto DPL) {
+        hipLaunchKernelGGL((cc_cos_fwd_kernel<A, B, DPL()>), grid, dim3(CC_THREADS), 0, st, (const A*)a, (const B*)b,
+                           patch_ids, U, nb, D, shift, cosv, stats);
+      });
+    });
+  });
   PTV3_LAUNCH_CHECK();
   hipLaunchKernelGGL(cc_cos_finish_kernel, dim3(1), dim3(CC_THREADS), 0, st, cosv, U, loss);
   PTV3_LAUNCH_CHECK();
@@ -451,21 +431,16 @@ extern "C" int ptv3_concerto_cos_bwd(const float* dloss, const void* a, int a_dt
   PTV3_REQUIRE(dloss && a && b && patch_ids && da, "concerto_cos_bwd: a pointer is NULL");
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)cdiv(U, CC_WAVES));
-#define CC_COSB(DPL)                                                                                                  \
-  if (a_dtype == PTV3_BF16 && b_dtype == PTV3_BF16)                                                                   \
-    hipLaunchKernelGGL((cc_cos_bwd_kernel<__bf16, __bf16, DPL>), grid, dim3(CC_THREADS), 0, st, dloss,                \
-                       (const __bf16*)a, (const __bf16*)b, patch_ids, U, nb, D, shift, (__bf16*)da);                  \
-  else if (a_dtype == PTV3_BF16)                                                                                      \
-    hipLaunchKernelGGL((cc_cos_bwd_kernel<__bf16, float, DPL>), grid, dim3(CC_THREADS), 0, st, dloss,                 \
-                       (const __bf16*)a, (const float*)b, patch_ids, U, nb, D, shift, (__bf16*)da);                   \
-  else if (b_dtype == PTV3_BF16)                                                                                      \
-    hipLaunchKernelGGL((cc_cos_bwd_kernel<float, __bf16, DPL>), grid, dim3(CC_THREADS), 0, st, dloss,                 \
-                       (const float*)a, (const __bf16*)b, patch_ids, U, nb, D, shift, (float*)da);                    \
-  else                                                                                                                \
-    hipLaunchKernelGGL((cc_cos_bwd_kernel<float, float, DPL>), grid, dim3(CC_THREADS), 0, st, dloss, (const float*)a, \
-                       (const float*)b, patch_ids, U, nb, D, shift, (float*)da)
-  CC_BY_D(D, CC_COSB);
-#undef CC_COSB
+  by_dtype(a_dtype, [&](auto ta) {
+    using A = typename decltype(ta)::type;
+    by_dtype(b_dtype, [&](auto tb) {
+      using B = typename decltype(tb)::type;
+      by_value<2, 8, 24, 32>(cc_dpl(D), [&](auto DPL) {
+        hipLaunchKernelGGL((cc_cos_bwd_kernel<A, B, DPL()>), grid, dim3(CC_THREADS), 0, st, dloss, (const A*)a,
+                           (const B*)b, patch_ids, U, nb, D, shift, (A*)da);
+      });
+    });
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }

@@ -237,20 +237,19 @@ extern "C" int ptv3_conv_head_halo(const void* x, const void* w, const float* co
   const HaloArgs h{p.count, p.rows, p.slots};
   const HeadArgs hd{nullptr, nullptr, 0, nullptr, shortcut, g0, b0, g1, b1, wqkv, bqkv, f1, qkv, m, eps};
   hipStream_t s = (hipStream_t)stream;
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
+  const int esz = dtype_bytes(dtype);
   const int prof = prof_begin(s, PROF_SUBM_CONV, 2.0 * m * HALO_TAPS * c * c + 2.0 * m * c * 3 * c,
                               ((double)m * c * 6 + (double)(HALO_TAPS + 3) * c * c) * esz, nbr, m * HALO_TAPS, 2.0 * c * c);
   prof_kernel(prof, PK_CONV_HEAD_HALO);
   const dim3 grid((unsigned)p.tiles);
-#define CH_LAUNCH(T, C_)                                                                                      \
-  do {                                                                                                        \
-    const int lds = HaloShape<T, C_>::LDS;                                                                    \
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_head_halo_kernel<T, C_>), lds);                    \
-    hipLaunchKernelGGL((conv_head_halo_kernel<T, C_>), grid, dim3(256), lds, s, a, h, hd);                    \
-  } while (0)
-  if (dtype == PTV3_F32) { if (c == 32) CH_LAUNCH(float, 32); else CH_LAUNCH(float, 64); }
-  else { if (c == 32) CH_LAUNCH(__bf16, 32); else CH_LAUNCH(__bf16, 64); }
-#undef CH_LAUNCH
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_value<32, 64>(c, [&](auto C) {
+      const int lds = HaloShape<T, C()>::LDS;
+      ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_head_halo_kernel<T, C()>), lds);
+      hipLaunchKernelGGL((conv_head_halo_kernel<T, C()>), grid, dim3(256), lds, s, a, h, hd);
+    });
+  });
   prof_end(prof, s);
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;

@@ -295,7 +295,7 @@ extern "C" int ptv3_stem_conv_blocks(const void* x, const void* w, void* out, in
                                      const int32_t* row_order, const float* bias, const float* bn_scale,
                                      const float* bn_shift, int act, int dtype, void* stream) {
   PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "stem_conv_blocks: bad dtype %d", dtype);
-  const int gran = dtype == PTV3_F32 ? 4 : 8;
+  const int gran = dtype_granule(dtype);
   PTV3_REQUIRE(cin > 0 && cin % gran == 0, "stem_conv_blocks: cin=%d must be a positive multiple of %d for this dtype", cin, gran);
   PTV3_REQUIRE(cout > 0, "stem_conv_blocks: cout=%d", cout);
   PTV3_REQUIRE(ksize == 3 || ksize == 5, "stem_conv_blocks: ksize %d must be 3 or 5", ksize);
@@ -320,21 +320,20 @@ extern "C" int ptv3_stem_conv_blocks(const void* x, const void* w, void* out, in
              ptv3_gemm_splits(n, cin, cout, kvol, dtype)};
   hipStream_t s = (hipStream_t)stream;
   const int nt = cout <= 32 ? 2 : 4;
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
+  const int esz = dtype_bytes(dtype);
   // flops of a full neighbourhood: the taps that exist are not counted anywhere without a table
   const int prof = prof_begin(s, PROF_SUBM_CONV, 2.0 * n * kvol * cin * cout,
                               ((double)n * cin + (double)cout * kvol * cin + (double)n * cout) * esz, nullptr, 0, 0.0);
   prof_kernel(prof, nt == 2 ? PK_GEMM32_CONV : PK_GEMM64_CONV);
   const dim3 grid((unsigned)cdiv(n, ST_BM), (unsigned)cdiv(cout, 16 * nt)), block(ST_THREADS);
-#define ST_LAUNCH(T, NT_, K_) hipLaunchKernelGGL((stem_conv_kernel<T, NT_, K_, ST_PD>), grid, block, 0, s, a, g)
-#define ST_PICK(T)                                                        \
-  do {                                                                    \
-    if (ksize == 5) { if (nt == 2) ST_LAUNCH(T, 2, 5); else ST_LAUNCH(T, 4, 5); } \
-    else { if (nt == 2) ST_LAUNCH(T, 2, 3); else ST_LAUNCH(T, 4, 3); }    \
-  } while (0)
-  if (dtype == PTV3_F32) ST_PICK(float); else ST_PICK(__bf16);
-#undef ST_PICK
-#undef ST_LAUNCH
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_value<2, 4>(nt, [&](auto NT) {
+      by_value<3, 5>(ksize, [&](auto K) {
+        hipLaunchKernelGGL((stem_conv_kernel<T, NT(), K(), ST_PD>), grid, block, 0, s, a, g);
+      });
+    });
+  });
   prof_end(prof, s);
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;

@@ -173,12 +173,7 @@ static void launch_nt(const ConvLnArgs& a, hipStream_t s) {
 
 template <typename T>
 static int launch_conv_ln(const ConvLnArgs& a, int cout, hipStream_t s) {
-  switch (cout) {
-    case 16: launch_nt<T, 1>(a, s); break;
-    case 32: launch_nt<T, 2>(a, s); break;
-    case 64: launch_nt<T, 4>(a, s); break;
-    default: launch_nt<T, 8>(a, s); break;
-  }
+  by_value<16, 32, 64, 128>(cout, [&](auto C) { launch_nt<T, C() / 16>(a, s); });   // width_ok()
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }
@@ -215,8 +210,9 @@ extern "C" int ptv3_subm_conv_ln(const void* x, const void* w, const int32_t* nb
   if (m == 0) return PTV3_OK;
   PTV3_REQUIRE(x && w && nbr && gamma && beta && out, "subm_conv_ln: x, w, nbr, gamma, beta and out are required");
   ConvLnArgs a{x, w, out, nbr, row_order, bias, gamma, beta, m, m, c, shift_of(c), kvol, act, eps};
-  if (dtype == PTV3_F32) return launch_conv_ln<float>(a, c, (hipStream_t)stream);
-  return launch_conv_ln<__bf16>(a, c, (hipStream_t)stream);
+  int rc = PTV3_OK;
+  by_dtype(dtype, [&](auto t) { rc = launch_conv_ln<typename decltype(t)::type>(a, c, (hipStream_t)stream); });
+  return rc;
 }
 
 extern "C" int ptv3_rows_linear_ln(const void* x, const void* w, const float* bias, const float* gamma,
@@ -232,6 +228,7 @@ extern "C" int ptv3_rows_linear_ln(const void* x, const void* w, const float* bi
   if (m == 0) return PTV3_OK;
   PTV3_REQUIRE(x && w && gamma && beta && out, "rows_linear_ln: x, w, gamma, beta and out are required");
   ConvLnArgs a{x, w, out, nullptr, nullptr, bias, gamma, beta, m, m, c, shift_of(c), 1, act, eps};
-  if (dtype == PTV3_F32) return launch_conv_ln<float>(a, cout, (hipStream_t)stream);
-  return launch_conv_ln<__bf16>(a, cout, (hipStream_t)stream);
+  int rc = PTV3_OK;
+  by_dtype(dtype, [&](auto t) { rc = launch_conv_ln<typename decltype(t)::type>(a, cout, (hipStream_t)stream); });
+  return rc;
 }

@@ -262,14 +262,13 @@ __global__ void pad_cast_kernel(const S* __restrict__ x, int cin, D* __restrict_
 }
 static void pad_cast(const void* x, int sdt, int cin, void* y, int ddt, int cpad, int64_t n, hipStream_t s) {
   dim3 grid((unsigned)cdiv(n * cpad, 256)), block(256);
-  if (sdt == PTV3_F32 && ddt == PTV3_F32)
-    hipLaunchKernelGGL((pad_cast_kernel<float, float>), grid, block, 0, s, (const float*)x, cin, (float*)y, cpad, n);
-  else if (sdt == PTV3_F32)
-    hipLaunchKernelGGL((pad_cast_kernel<float, __bf16>), grid, block, 0, s, (const float*)x, cin, (__bf16*)y, cpad, n);
-  else if (ddt == PTV3_F32)
-    hipLaunchKernelGGL((pad_cast_kernel<__bf16, float>), grid, block, 0, s, (const __bf16*)x, cin, (float*)y, cpad, n);
-  else
-    hipLaunchKernelGGL((pad_cast_kernel<__bf16, __bf16>), grid, block, 0, s, (const __bf16*)x, cin, (__bf16*)y, cpad, n);
+  by_dtype(sdt, [&](auto ts) {
+    using S = typename decltype(ts)::type;
+    by_dtype(ddt, [&](auto td) {
+      using D = typename decltype(td)::type;
+      hipLaunchKernelGGL((pad_cast_kernel<S, D>), grid, block, 0, s, (const S*)x, cin, (D*)y, cpad, n);
+    });
+  });
 }
 
 struct Run {
@@ -524,7 +523,7 @@ struct Run {
 static int run_forward(Exec* X, const ptv3_model_desc* d, const void* const* params, const ptv3_forward_io* io, Arena& G,
                        Arena& F, hipStream_t sf, bool dry, int* param_count = nullptr) {
   Run R; R.X = X; R.d = d; R.params = params; R.G = &G; R.F = &F; R.sf = sf; R.dry = dry;
-  R.es = d->dtype == PTV3_F32 ? 4 : 2;
+  R.es = dtype_bytes(d->dtype);
   const int S = d->num_stages, k = d->num_orders, es = R.es;
   if (!dry) {
     if (!X->geo) {

@@ -1045,7 +1045,7 @@ extern "C" int ptv3_gemm(const void* x, const void* w, void* out, int64_t m, int
                          const int32_t* res_index, void* out2, int dtype, void* workspace,
                          size_t workspace_bytes, void* stream) {
   PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "gemm: bad dtype %d", dtype);
-  const int gran = dtype == PTV3_F32 ? 4 : 8;
+  const int gran = dtype_granule(dtype);
   PTV3_REQUIRE(cin > 0 && cin % gran == 0, "gemm: cin=%d must be a positive multiple of %d for this dtype", cin, gran);
   PTV3_REQUIRE(cout > 0, "gemm: cout=%d", cout);
   PTV3_REQUIRE(kvol >= 1 && (kvol == 1 || nbr != nullptr), "gemm: kvol=%d needs a neighbour table", kvol);
@@ -1075,7 +1075,7 @@ extern "C" int ptv3_gemm(const void* x, const void* w, void* out, int64_t m, int
   // gathered rows through a buffer descriptor (missing neighbours cost no memory access): x is the (m, cin) feature
   // matrix of the m active sites the neighbour table was built for, and both operands must be addressable with 32-bit
   // byte offsets.  PTV3_GEMM_BUF=0 keeps the pointer form (tools/bench_gemm_big.py compares them).
-  const int esz0 = dtype == PTV3_F32 ? 4 : 2;
+  const int esz0 = dtype_bytes(dtype);
   const char* buf_env = getenv("PTV3_GEMM_BUF");
   const bool buf_on = !(buf_env && atoi(buf_env) == 0);
   const int64_t xb = m * cin * esz0, wb = (int64_t)cout * kvol * cin * esz0, lim = ((int64_t)1 << 31) - 4096;
@@ -1087,7 +1087,7 @@ extern "C" int ptv3_gemm(const void* x, const void* w, void* out, int64_t m, int
   int nt = choose_nt(cout);
   if (nbr && nt != 2) nt = 4;
   const int bn = 16 * nt;
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
+  const int esz = dtype_bytes(dtype);
   const int prof = prof_begin(s, nbr ? PROF_SUBM_CONV : PROF_LINEAR, 2.0 * m * kvol * cin * cout,
                               ((double)m * cin * (nbr ? 1 : kvol) + (double)cout * kvol * cin +
                                (double)m * cout * (1 + (res != nullptr) + (out2 != nullptr))) * esz,
@@ -1096,10 +1096,10 @@ extern "C" int ptv3_gemm(const void* x, const void* w, void* out, int64_t m, int
     GemmArgs r = a;
     r.row_order = nullptr;  // slabs are indexed by output row already
     const int64_t work = m * ((cout + 3) / 4);
-    if (dtype == PTV3_F32)
-      hipLaunchKernelGGL(splitk_reduce_kernel<float>, dim3((unsigned)cdiv(work, 256)), dim3(256), 0, s, r, splits);
-    else
-      hipLaunchKernelGGL(splitk_reduce_kernel<__bf16>, dim3((unsigned)cdiv(work, 256)), dim3(256), 0, s, r, splits);
+    by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      hipLaunchKernelGGL(splitk_reduce_kernel<T>, dim3((unsigned)cdiv(work, 256)), dim3(256), 0, s, r, splits);
+    });
   };
   int ct_bn = 0;
   const bool ctile = nbr != nullptr && (out != nullptr || splits > 1) && use_conv_tile(m, cin, cout, kvol, dtype, x_bytes, &ct_bn, splits);
@@ -1114,19 +1114,20 @@ extern "C" int ptv3_gemm(const void* x, const void* w, void* out, int64_t m, int
     const size_t lds = std::max(lds_ops, lds_out) + (size_t)3 * ct_bn * sizeof(float);
     PTV3_REQUIRE(lds <= 160 * 1024, "conv tile: %zu bytes of LDS", lds);
     dim3 cgrid((unsigned)(cdiv(m, GC_BM) * cdiv(cout, ct_bn)), (unsigned)std::max(splits, 1));
-#define GC_LAUNCH(T, BN_, KB_, NS_)                                                                              \
-    do {                                                                                                         \
-      ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_tile_kernel<T, BN_, KB_, NS_>), 160 * 1024);        \
-      hipLaunchKernelGGL((conv_tile_kernel<T, BN_, KB_, NS_>), cgrid, gc_threads, lds, s, a);              \
-    } while (0)
-#define GC_PICK(T, BN_) do { if (four) GC_LAUNCH(T, BN_, 64, 4); else GC_LAUNCH(T, BN_, 128, 2); } while (0)
     const dim3 gc_threads(ct_bn == 64 ? GC_THREADS / 2 : GC_THREADS);
-    if (dtype == PTV3_F32) GC_PICK(float, 128);
-    else if (ct_bn == 256) GC_PICK(__bf16, 256);
-    else if (ct_bn == 64) GC_PICK(__bf16, 64);
-    else GC_PICK(__bf16, 128);
-#undef GC_PICK
-#undef GC_LAUNCH
+    // fp32 has the 128-channel tile only (use_conv_tile gives it no other width)
+    by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      by_value<64, 128, 256>(ct_bn, [&](auto BN) {
+        by_value<2, 4>(four ? 4 : 2, [&](auto NS) {
+          if constexpr (std::is_same_v<T, __bf16> || BN() == 128) {
+            constexpr int KB = 256 / NS();   // bytes of K per stage
+            ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_tile_kernel<T, BN(), KB, NS()>), 160 * 1024);
+            hipLaunchKernelGGL((conv_tile_kernel<T, BN(), KB, NS()>), cgrid, gc_threads, lds, s, a);
+          }
+        });
+      });
+    });
     prof_end(prof, s);
     if (splits > 1 && out != nullptr) reduce_slabs();
     PTV3_LAUNCH_CHECK();
@@ -1140,34 +1141,23 @@ extern "C" int ptv3_gemm(const void* x, const void* w, void* out, int64_t m, int
     static_assert(2 * (GB_BM + 128) * 128 + GB_BM * GB_MAX_KVOL * 4 + GB_MAX_STEPS + 32 + 3 * 128 * 4 <= 80 * 1024,
                   "gemm_big_kernel: two workgroups per CU need <= 80 KB of LDS each");
     dim3 bgrid((unsigned)(cdiv(m, GB_BM) * cdiv(cout, big_bn)));
-#define GB_LAUNCH(T, WM_, WN_, BN_, G_, B_)                                                                      \
-    do {                                                                                                         \
-      ensure_dynamic_lds(reinterpret_cast<const void*>(&gemm_big_kernel<T, WM_, WN_, BN_, G_, B_>), 96 * 1024);  \
-      hipLaunchKernelGGL((gemm_big_kernel<T, WM_, WN_, BN_, G_, B_>), bgrid, dim3(GB_THREADS), lds, s, a);       \
-    } while (0)
-#define GB_PICK(T)                                                                                               \
-    do {                                                                                                         \
-      if (nbr && x_bytes) { if (big_bn == 128) GB_LAUNCH(T, 2, 2, 128, true, true); else GB_LAUNCH(T, 4, 1, 64, true, true); } \
-      else if (nbr) { if (big_bn == 128) GB_LAUNCH(T, 2, 2, 128, true, false); else GB_LAUNCH(T, 4, 1, 64, true, false); }     \
-      else { if (big_bn == 128) GB_LAUNCH(T, 2, 2, 128, false, false); else GB_LAUNCH(T, 4, 1, 64, false, false); }            \
-    } while (0)
-    if (dtype == PTV3_F32) GB_PICK(float); else GB_PICK(__bf16);
-#undef GB_PICK
-#undef GB_LAUNCH
+    // operands: 0 dense, 1 gathered through pointers, 2 gathered through the buffer descriptor
+    by_dtype(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      by_value<64, 128>(big_bn, [&](auto BN) {
+        by_value<0, 1, 2>(nbr ? (x_bytes ? 2 : 1) : 0, [&](auto G) {
+          constexpr int WM = BN() == 128 ? 2 : 4, WN = BN() == 128 ? 2 : 1;
+          constexpr auto kernel = gemm_big_kernel<T, WM, WN, BN(), G() != 0, G() == 2>;
+          ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), 96 * 1024);
+          hipLaunchKernelGGL(kernel, bgrid, dim3(GB_THREADS), lds, s, a);
+        });
+      });
+    });
     prof_end(prof, s);
     PTV3_LAUNCH_CHECK();
     return PTV3_OK;
   }
   dim3 grid((unsigned)cdiv(m, GM_BM), (unsigned)cdiv(cout, bn), (unsigned)splits);
-#define GM_LAUNCH(T, G)                                                                                \
-  switch (nt) {                                                                                        \
-    case 2: hipLaunchKernelGGL((gemm_kernel<T, 2, G>), grid, dim3(GM_THREADS), 0, s, a); break;        \
-    case 4: hipLaunchKernelGGL((gemm_kernel<T, 4, G>), grid, dim3(GM_THREADS), 0, s, a); break;        \
-    case 6: hipLaunchKernelGGL((gemm_kernel<T, 6, G>), grid, dim3(GM_THREADS), 0, s, a); break;        \
-    case 8: hipLaunchKernelGGL((gemm_kernel<T, 8, G>), grid, dim3(GM_THREADS), 0, s, a); break;        \
-    case 12: hipLaunchKernelGGL((gemm_kernel<T, 12, G>), grid, dim3(GM_THREADS), 0, s, a); break;      \
-    default: hipLaunchKernelGGL((gemm_kernel<T, 16, G>), grid, dim3(GM_THREADS), 0, s, a); break;      \
-  }
   // small grids (the deep levels): four K stages in flight per workgroup instead of one
   // register-ring depth: 4 for the small grids of the deep levels, PTV3_GEMM_PD_LARGE (default 1) for chip-filling ones
   const char* pd_env = getenv("PTV3_GEMM_PD");
@@ -1178,26 +1168,20 @@ extern "C" int ptv3_gemm(const void* x, const void* w, void* out, int64_t m, int
     pd = pd_env ? atoi(pd_env) : (small ? 4 : (pdl_env ? atoi(pdl_env) : 1));
     if (pd != 2 && pd != 4) pd = 1;
   }
-#define GM_PD(T, G)                                                                                            \
-  do {                                                                                                         \
-    if (pd == 4) hipLaunchKernelGGL((gemm_kernel<T, 4, G, 4>), grid, dim3(GM_THREADS), 0, s, a);               \
-    else if (pd == 2) hipLaunchKernelGGL((gemm_kernel<T, 4, G, 2>), grid, dim3(GM_THREADS), 0, s, a);          \
-    else hipLaunchKernelGGL((gemm_kernel<T, 4, G, 1>), grid, dim3(GM_THREADS), 0, s, a);                       \
-  } while (0)
-  if (nbr) {
-    // the gathered instantiations only exist for the tile widths the policy picks (2, 4)
-    if (dtype == PTV3_F32) {
-      if (nt == 2) hipLaunchKernelGGL((gemm_kernel<float, 2, true>), grid, dim3(GM_THREADS), 0, s, a);
-      else GM_PD(float, true);
-    } else {
-      if (nt == 2) hipLaunchKernelGGL((gemm_kernel<__bf16, 2, true>), grid, dim3(GM_THREADS), 0, s, a);
-      else GM_PD(__bf16, true);
-    }
-  } else if (nt == 4) {
-    if (dtype == PTV3_F32) GM_PD(float, false); else GM_PD(__bf16, false);
-  } else if (dtype == PTV3_F32) { GM_LAUNCH(float, false) } else { GM_LAUNCH(__bf16, false) }
-#undef GM_PD
-#undef GM_LAUNCH
+  // the gathered instantiations only exist for the tile widths the policy picks (2, 4); the ring depth only at 4
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_value<0, 1>(nbr != nullptr, [&](auto G) {
+      by_value<2, 4, 6, 8, 12, 16>(nt, [&](auto NT) {
+        if constexpr (NT() == 4)
+          by_value<1, 2, 4>(pd, [&](auto PD) {
+            hipLaunchKernelGGL((gemm_kernel<T, 4, G() != 0, PD()>), grid, dim3(GM_THREADS), 0, s, a);
+          });
+        else if constexpr (!G() || NT() == 2)
+          hipLaunchKernelGGL((gemm_kernel<T, NT(), G() != 0>), grid, dim3(GM_THREADS), 0, s, a);
+      });
+    });
+  });
   prof_end(prof, s);   // the bracket times the GEMM launch alone (the slab reduce below is its own, tiny kernel)
   if (splits > 1 && out != nullptr) reduce_slabs();
   PTV3_LAUNCH_CHECK();
@@ -1226,22 +1210,21 @@ extern "C" int ptv3_conv_halo(const void* x, const void* w, void* out, int64_t m
              m, c, c, HALO_TAPS, act, c == 32 ? 5 : 6, 0, 0, 0};
   const HaloArgs h{p.count, p.rows, p.slots};
   hipStream_t s = (hipStream_t)stream;
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
+  const int esz = dtype_bytes(dtype);
   const int prof = prof_begin(s, PROF_SUBM_CONV, 2.0 * m * HALO_TAPS * c * c,
                               ((double)m * c + (double)HALO_TAPS * c * c +
                                (double)m * c * (1 + (res != nullptr) + (out2 != nullptr))) * esz,
                               nbr, m * HALO_TAPS, 2.0 * c * c);
   prof_kernel(prof, PK_CONV_HALO);
   const dim3 grid((unsigned)p.tiles);
-#define HC_LAUNCH(T, C_)                                                                                      \
-  do {                                                                                                        \
-    const int lds = HaloShape<T, C_>::LDS;                                                                    \
-    ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_halo_kernel<T, C_>), lds);                         \
-    hipLaunchKernelGGL((conv_halo_kernel<T, C_>), grid, dim3(256), lds, s, a, h);                             \
-  } while (0)
-  if (dtype == PTV3_F32) { if (c == 32) HC_LAUNCH(float, 32); else HC_LAUNCH(float, 64); }
-  else { if (c == 32) HC_LAUNCH(__bf16, 32); else HC_LAUNCH(__bf16, 64); }
-#undef HC_LAUNCH
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_value<32, 64>(c, [&](auto C) {
+      const int lds = HaloShape<T, C()>::LDS;
+      ensure_dynamic_lds(reinterpret_cast<const void*>(&conv_halo_kernel<T, C()>), lds);
+      hipLaunchKernelGGL((conv_halo_kernel<T, C()>), grid, dim3(256), lds, s, a, h);
+    });
+  });
   prof_end(prof, s);
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;

@@ -238,12 +238,11 @@ void scene_mean_partial(const void* feat, const int64_t* offset, int64_t n, int 
                         hipStream_t s) {
   const int64_t rb = scene_rows_per_chunk(n);
   const dim3 grid((unsigned)scene_chunks(n, b));
-  if (dtype == PTV3_F32)
-    hipLaunchKernelGGL(scene_mean_partial_kernel<float>, grid, dim3(SM_THREADS), 0, s, (const float*)feat, offset, b,
-                       n, c, rb, slab);
-  else
-    hipLaunchKernelGGL(scene_mean_partial_kernel<__bf16>, grid, dim3(SM_THREADS), 0, s, (const __bf16*)feat, offset, b,
-                       n, c, rb, slab);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(scene_mean_partial_kernel<T>, grid, dim3(SM_THREADS), 0, s, (const T*)feat, offset, b, n, c, rb,
+                       slab);
+  });
 }
 
 }  // namespace ptv3
@@ -299,15 +298,14 @@ extern "C" int ptv3_scene_mean_bwd(const float* dg, const int64_t* offset, int64
   PTV3_REQUIRE(n == 0 || b == 0 || (dg && offset), "scene_mean_bwd: dg / offset is NULL");
   if (n == 0) return PTV3_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int64_t items = n * (c / (dtype == PTV3_F32 ? 4 : 8));
+  const int64_t items = n * (c / dtype_granule(dtype));
   int64_t blocks = cdiv(items, SM_THREADS);
   if (blocks > 2048) blocks = 2048;
-  if (dtype == PTV3_F32)
-    hipLaunchKernelGGL(scene_mean_bwd_kernel<float>, dim3((unsigned)blocks), dim3(SM_THREADS), 0, s, dg, offset, b, n,
-                       c, (float*)dfeat);
-  else
-    hipLaunchKernelGGL(scene_mean_bwd_kernel<__bf16>, dim3((unsigned)blocks), dim3(SM_THREADS), 0, s, dg, offset, b, n,
-                       c, (__bf16*)dfeat);
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(scene_mean_bwd_kernel<T>, dim3((unsigned)blocks), dim3(SM_THREADS), 0, s, dg, offset, b, n, c,
+                       (T*)dfeat);
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }

@@ -154,32 +154,18 @@ static int launch_ln(const void* x, const float* gamma, const float* beta, const
   const int nch = c / 4;
   int lpr = 1;
   while (lpr < 64 && lpr < nch) lpr <<= 1;
-#define LN_LAUNCH_NK(L, NK)                                                                              \
-  {                                                                                                      \
-    int64_t rows_per_block = 4 * (64 / L);                                                               \
-    hipLaunchKernelGGL((layernorm_kernel<T, L, NK>), dim3((unsigned)cdiv(m, rows_per_block)), dim3(256), 0, s, \
-                       (const T*)x, gamma, beta, (const T*)res, (T*)y, gamma2, beta2, (T*)y2, m, c, eps, slab,   \
-                       splits, slab_bias);                                                                \
-  }
-#define LN_LAUNCH(L) \
-  if (slab) LN_LAUNCH_NK(L, 1) else LN_LAUNCH_NK(L, 0)
-  if (slab && nch > 64) {  // slab input with more than one chunk per lane
-    if (nch <= 128) LN_LAUNCH_NK(64, 2)
-    else if (nch <= 256) LN_LAUNCH_NK(64, 4)
-    else LN_LAUNCH_NK(64, 8)
-  } else {
-    switch (lpr) {
-      case 1: LN_LAUNCH(1) break;
-      case 2: LN_LAUNCH(2) break;
-      case 4: LN_LAUNCH(4) break;
-      case 8: LN_LAUNCH(8) break;
-      case 16: LN_LAUNCH(16) break;
-      case 32: LN_LAUNCH(32) break;
-      default: LN_LAUNCH(64) break;
-    }
-  }
-#undef LN_LAUNCH
-#undef LN_LAUNCH_NK
+  // chunks per lane of a slab input: 0 without slabs; more than one only at 64 lanes per row (nch > 64)
+  const int nk = !slab ? 0 : nch <= 64 ? 1 : nch <= 128 ? 2 : nch <= 256 ? 4 : 8;
+  by_value<1, 2, 4, 8, 16, 32, 64>(lpr, [&](auto L) {
+    by_value<0, 1, 2, 4, 8>(nk, [&](auto NK) {
+      if constexpr (NK() <= 1 || L() == 64) {
+        const int64_t rows_per_block = 4 * (64 / L());
+        hipLaunchKernelGGL((layernorm_kernel<T, L(), NK()>), dim3((unsigned)cdiv(m, rows_per_block)), dim3(256), 0, s,
+                           (const T*)x, gamma, beta, (const T*)res, (T*)y, gamma2, beta2, (T*)y2, m, c, eps, slab,
+                           splits, slab_bias);
+      }
+    });
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }
@@ -195,8 +181,11 @@ extern "C" int ptv3_layernorm(const void* x, const float* gamma, const float* be
   PTV3_REQUIRE((y2 == nullptr) || (gamma2 && beta2), "layernorm: y2 needs gamma2/beta2");
   PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "layernorm: bad dtype");
   if (m == 0) return PTV3_OK;
-  if (dtype == PTV3_F32) return launch_ln<float>(x, gamma, beta, res, y, gamma2, beta2, y2, m, c, eps, (hipStream_t)stream);
-  return launch_ln<__bf16>(x, gamma, beta, res, y, gamma2, beta2, y2, m, c, eps, (hipStream_t)stream);
+  int rc = PTV3_OK;
+  by_dtype(dtype, [&](auto t) {
+    rc = launch_ln<typename decltype(t)::type>(x, gamma, beta, res, y, gamma2, beta2, y2, m, c, eps, (hipStream_t)stream);
+  });
+  return rc;
 }
 
 extern "C" int ptv3_layernorm_slabs(const float* slab, int splits, const float* slab_bias, const float* gamma,
@@ -210,11 +199,12 @@ extern "C" int ptv3_layernorm_slabs(const float* slab, int splits, const float* 
   PTV3_REQUIRE((y2 == nullptr) || (gamma2 && beta2), "layernorm_slabs: y2 needs gamma2/beta2");
   PTV3_REQUIRE(dtype == PTV3_F32 || dtype == PTV3_BF16, "layernorm_slabs: bad dtype");
   if (m == 0) return PTV3_OK;
-  if (dtype == PTV3_F32)
-    return launch_ln<float>(nullptr, gamma, beta, res, y, gamma2, beta2, y2, m, c, eps, (hipStream_t)stream, slab, splits,
-                            slab_bias);
-  return launch_ln<__bf16>(nullptr, gamma, beta, res, y, gamma2, beta2, y2, m, c, eps, (hipStream_t)stream, slab, splits,
-                           slab_bias);
+  int rc = PTV3_OK;
+  by_dtype(dtype, [&](auto t) {
+    rc = launch_ln<typename decltype(t)::type>(nullptr, gamma, beta, res, y, gamma2, beta2, y2, m, c, eps,
+                                               (hipStream_t)stream, slab, splits, slab_bias);
+  });
+  return rc;
 }
 
 extern "C" int ptv3_affine_act(const void* x, const float* scale, const float* shift, int act, void* y,
@@ -225,10 +215,11 @@ extern "C" int ptv3_affine_act(const void* x, const float* scale, const float* s
   int64_t total4 = m * c / 4;
   dim3 grid((unsigned)cdiv(total4, 256)), block(256);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == PTV3_F32)
-    hipLaunchKernelGGL(affine_act_kernel<float>, grid, block, 0, s, (const float*)x, scale, shift, act, (float*)y, total4, c);
-  else
-    hipLaunchKernelGGL(affine_act_kernel<__bf16>, grid, block, 0, s, (const __bf16*)x, scale, shift, act, (__bf16*)y, total4, c);
+  const bool known = by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(affine_act_kernel<T>, grid, block, 0, s, (const T*)x, scale, shift, act, (T*)y, total4, c);
+  });
+  PTV3_REQUIRE(known, "affine_act: bad dtype %d", dtype);
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }

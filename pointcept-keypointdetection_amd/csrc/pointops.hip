@@ -340,14 +340,14 @@ extern "C" int ptv3_knn_query(int m, int nsample, const float* xyz, const float*
   int nq = forced == 1 || forced == 2 || forced == 4 ? forced : (m >= 16384 ? 4 : m >= 4096 ? 2 : 1);
   if (nsample > 64 && nq > 2) nq = 2;
   dim3 grid((unsigned)cdiv(m, 4 * nq)), block(256);
-#define KNN_LAUNCH(KPL, NQ) \
-  hipLaunchKernelGGL((knn_query_kernel<KPL, NQ>), grid, block, 0, s, m, nsample, xyz, new_xyz, offset, new_offset, b, idx, dist2)
-  if (nsample <= 64) {
-    if (nq == 4) KNN_LAUNCH(1, 4); else if (nq == 2) KNN_LAUNCH(1, 2); else KNN_LAUNCH(1, 1);
-  } else {
-    if (nq == 2) KNN_LAUNCH(2, 2); else KNN_LAUNCH(2, 1);
-  }
-#undef KNN_LAUNCH
+  // two candidates per lane (nsample > 64) exist at one and two queries per wave only
+  by_value<1, 2>(nsample <= 64 ? 1 : 2, [&](auto KPL) {
+    by_value<1, 2, 4>(nq, [&](auto NQ) {
+      if constexpr (KPL() == 1 || NQ() <= 2)
+        hipLaunchKernelGGL((knn_query_kernel<KPL(), NQ()>), grid, block, 0, s, m, nsample, xyz, new_xyz, offset,
+                           new_offset, b, idx, dist2);
+    });
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }

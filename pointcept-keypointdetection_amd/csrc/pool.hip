@@ -228,19 +228,10 @@ static int launch_pool_feat(const void* feat, const int64_t* order0, const int32
   const int nch = c / 4;
   int lpr = 1;
   while (lpr < 64 && lpr < nch) lpr <<= 1;
-#define PF_LAUNCH(L)                                                                                          \
-  hipLaunchKernelGGL((pool_feat_kernel<T, L>), dim3((unsigned)cdiv(n_out, 4 * (64 / L))), dim3(256), 0, s,   \
-                     (const T*)feat, order0, seg_start, n_out, c, bn_scale, bn_shift, act, (T*)out);
-  switch (lpr) {
-    case 1: PF_LAUNCH(1) break;
-    case 2: PF_LAUNCH(2) break;
-    case 4: PF_LAUNCH(4) break;
-    case 8: PF_LAUNCH(8) break;
-    case 16: PF_LAUNCH(16) break;
-    case 32: PF_LAUNCH(32) break;
-    default: PF_LAUNCH(64) break;
-  }
-#undef PF_LAUNCH
+  by_value<1, 2, 4, 8, 16, 32, 64>(lpr, [&](auto L) {
+    hipLaunchKernelGGL((pool_feat_kernel<T, L()>), dim3((unsigned)cdiv(n_out, 4 * (64 / L()))), dim3(256), 0, s,
+                       (const T*)feat, order0, seg_start, n_out, c, bn_scale, bn_shift, act, (T*)out);
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }
@@ -265,9 +256,11 @@ extern "C" int ptv3_pool_reduce(const void* feat, const float* coord, const int6
   if (n_out == 0) return PTV3_OK;
   hipStream_t s = (hipStream_t)stream;
   if (feat != nullptr) {  // feature half (segmented max + folded BN + act)
-    int rc = dtype == PTV3_F32
-                 ? launch_pool_feat<float>(feat, order0, seg_start, n_out, c, bn_scale, bn_shift, act, feat_out, s)
-                 : launch_pool_feat<__bf16>(feat, order0, seg_start, n_out, c, bn_scale, bn_shift, act, feat_out, s);
+    int rc = PTV3_OK;
+    by_dtype(dtype, [&](auto t) {
+      rc = launch_pool_feat<typename decltype(t)::type>(feat, order0, seg_start, n_out, c, bn_scale, bn_shift, act,
+                                                        feat_out, s);
+    });
     if (rc) return rc;
   }
   if (grid_coord != nullptr) {  // geometry half (coord mean, head gathers, pooled codes)

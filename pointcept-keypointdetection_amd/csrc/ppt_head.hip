@@ -176,16 +176,7 @@ extern "C" int ptv3_ppt_head_fwd(const float* x, const float* B, const float* bi
   PTV3_REQUIRE(((uintptr_t)x & 15) == 0, "ppt_head_fwd: x must be 16-byte aligned");
   if (n == 0) return PTV3_OK;
   hipStream_t st = (hipStream_t)stream;
-  switch (C / 16) {
-    case 1: ppt_launch<1>(x, B, bias, beta, s, n, K, out, st); break;
-    case 2: ppt_launch<2>(x, B, bias, beta, s, n, K, out, st); break;
-    case 3: ppt_launch<3>(x, B, bias, beta, s, n, K, out, st); break;
-    case 4: ppt_launch<4>(x, B, bias, beta, s, n, K, out, st); break;
-    case 5: ppt_launch<5>(x, B, bias, beta, s, n, K, out, st); break;
-    case 6: ppt_launch<6>(x, B, bias, beta, s, n, K, out, st); break;
-    case 7: ppt_launch<7>(x, B, bias, beta, s, n, K, out, st); break;
-    default: ppt_launch<8>(x, B, bias, beta, s, n, K, out, st); break;
-  }
+  by_value<1, 2, 3, 4, 5, 6, 7, 8>(C / 16, [&](auto NT) { ppt_launch<NT()>(x, B, bias, beta, s, n, K, out, st); });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }

@@ -324,13 +324,7 @@ extern "C" int ptv3_res_conv(const float* xa, const float* xb, const float* w, c
   ResConvArgs a{xa, xb, w, w_proj, nbr, row_order, bn_scale, bn_shift, res, proj_scale, proj_shift, out, proj_out,
                 m, ca, cb, cout, act};
   hipStream_t s = (hipStream_t)stream;
-  switch (rc_nt(cout)) {
-    case 1: launch_nt<1>(a, s); break;
-    case 2: launch_nt<2>(a, s); break;
-    case 4: launch_nt<4>(a, s); break;
-    case 6: launch_nt<6>(a, s); break;
-    default: launch_nt<8>(a, s); break;
-  }
+  by_value<1, 2, 4, 6, 8>(rc_nt(cout), [&](auto NT) { launch_nt<NT()>(a, s); });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }

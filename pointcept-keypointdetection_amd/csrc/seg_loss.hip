@@ -415,16 +415,6 @@ static int seg_loss_check(const char* who, const void* logits, const void* label
 
 using namespace ptv3;
 
-#define SL_DISPATCH_G(g, LAUNCH) \
-  switch (g) {                   \
-    case 2: LAUNCH(2); break;    \
-    case 4: LAUNCH(4); break;    \
-    case 8: LAUNCH(8); break;    \
-    case 16: LAUNCH(16); break;  \
-    case 32: LAUNCH(32); break;  \
-    default: LAUNCH(64); break;  \
-  }
-
 extern "C" int ptv3_lovasz_scan_tile(void) { return SL_TILE; }
 
 // keys (C, n) u64 | inverse (C, n) i64 | tile counts (C, nt) i32 | slab (C, nt) f64 | the sort's own workspace
@@ -456,11 +446,10 @@ extern "C" int ptv3_lovasz_fwd(const float* logits, const int64_t* labels, int64
   char* sort_ws = ws + 2 * kb + sl_align256((size_t)C * nt * 4) + sl_align256((size_t)C * nt * 8);
   if (n > 0) {
     const int g = sl_group(C);
-#define SL_PREP(GG)                                                                                              \
-  hipLaunchKernelGGL(lovasz_prep_kernel<GG>, dim3(sl_row_blocks(n, GG)), dim3(SL_THREADS), 0, s, logits, labels, n, C, \
-                     ignore_index, keys)
-    SL_DISPATCH_G(g, SL_PREP)
-#undef SL_PREP
+    by_value<2, 4, 8, 16, 32, 64>(g, [&](auto G) {
+      hipLaunchKernelGGL(lovasz_prep_kernel<G()>, dim3(sl_row_blocks(n, G())), dim3(SL_THREADS), 0, s, logits, labels, n,
+                         C, ignore_index, keys);
+    });
     const int src = ptv3_argsort_i64((const int64_t*)keys, C, n, 33, order, inverse, sort_ws,
                                      ptv3_argsort_workspace_bytes(C, n), stream);
     if (src != PTV3_OK) return src;
@@ -487,11 +476,10 @@ extern "C" int ptv3_lovasz_bwd(const float* dloss, const float* logits, const in
   if (n == 0) return PTV3_OK;
   hipStream_t s = (hipStream_t)stream;
   const int g = sl_group(C);
-#define SL_BWD(GG)                                                                                                 \
-  hipLaunchKernelGGL(lovasz_bwd_kernel<GG>, dim3(sl_row_blocks(n, GG)), dim3(SL_THREADS), 0, s, dloss, logits, labels, \
-                     weight, count, n, C, ignore_index, loss_weight, dlogits)
-  SL_DISPATCH_G(g, SL_BWD)
-#undef SL_BWD
+  by_value<2, 4, 8, 16, 32, 64>(g, [&](auto G) {
+    hipLaunchKernelGGL(lovasz_bwd_kernel<G()>, dim3(sl_row_blocks(n, G())), dim3(SL_THREADS), 0, s, dloss, logits, labels,
+                       weight, count, n, C, ignore_index, loss_weight, dlogits);
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }

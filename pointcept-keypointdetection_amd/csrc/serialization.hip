@@ -485,16 +485,14 @@ static int argsort_run(const int64_t* code, int k, int64_t n, int end_bit, int64
     if (!fused) hipLaunchKernelGGL(radix_scan_kernel, dim3(k), dim3(256 * RSC_PARTS), 0, s, hist, nblk);
     uint64_t* kout = kbuf[p & 1];
     uint32_t* vout = vbuf[p & 1];
-#define RS_SCATTER(F, L)                                                                                          \
-    if (fused) hipLaunchKernelGGL((radix_scatter_kernel<F, L, true>), grid, block, 0, s, kin, vin, kout, vout, order, \
-                                  inverse, row_order, n, shift, hist, nblk);                                      \
-    else hipLaunchKernelGGL((radix_scatter_kernel<F, L, false>), grid, block, 0, s, kin, vin, kout, vout, order,  \
-                            inverse, row_order, n, shift, hist, nblk)
-    if (first && last) { RS_SCATTER(true, true); }
-    else if (first) { RS_SCATTER(true, false); }
-    else if (last) { RS_SCATTER(false, true); }
-    else { RS_SCATTER(false, false); }
-#undef RS_SCATTER
+    by_value<0, 1>(first, [&](auto F) {
+      by_value<0, 1>(last, [&](auto L) {
+        by_value<0, 1>(fused, [&](auto FS) {
+          hipLaunchKernelGGL((radix_scatter_kernel<F() != 0, L() != 0, FS() != 0>), grid, block, 0, s, kin, vin, kout,
+                             vout, order, inverse, row_order, n, shift, hist, nblk);
+        });
+      });
+    });
     kin = kout;
     vin = vout;
   }

@@ -397,12 +397,7 @@ static bool sn_finite(double v) { return v == v && v - v == 0.0; }
 using namespace ptv3;
 
 // KPL = entries per lane: 64 * KPL >= K
-#define SN_BY_K(K, CALL)                 \
-  do {                                   \
-    if ((K) <= 128) { CALL(2); }         \
-    else if ((K) <= 1024) { CALL(16); }  \
-    else { CALL(64); }                   \
-  } while (0)
+static int sn_kpl(int K) { return K <= 128 ? 2 : K <= 1024 ? 16 : 64; }
 
 extern "C" int ptv3_sonata_capable(int K) { return K >= 2 && K <= SN_MAX_K; }
 
@@ -429,15 +424,13 @@ extern "C" int ptv3_sonata_sk_pass(const void* x, int x_dtype, const void* idx_t
   sn_split(inv_temp, &hi, &lo);
   const double inv_n = u ? 1.0 / n_total : 1.0;
   float* slab = (float*)workspace;
-#define SN_SK(KPL)                                                                                                    \
-  if (x_dtype == PTV3_BF16)                                                                                           \
-    hipLaunchKernelGGL((sn_sk_partial_kernel<__bf16, KPL>), dim3((unsigned)chunks), dim3(SN_THREADS), 0, st,          \
-                       (const __bf16*)x, idx_t, idx_i32, nt, M, K, hi, lo, u, inv_n, slab);                           \
-  else                                                                                                                \
-    hipLaunchKernelGGL((sn_sk_partial_kernel<float, KPL>), dim3((unsigned)chunks), dim3(SN_THREADS), 0, st,           \
-                       (const float*)x, idx_t, idx_i32, nt, M, K, hi, lo, u, inv_n, slab)
-  SN_BY_K(K, SN_SK);
-#undef SN_SK
+  by_dtype(x_dtype, [&](auto tx) {
+    using X = typename decltype(tx)::type;
+    by_value<2, 16, 64>(sn_kpl(K), [&](auto KPL) {
+      hipLaunchKernelGGL((sn_sk_partial_kernel<X, KPL()>), dim3((unsigned)chunks), dim3(SN_THREADS), 0, st, (const X*)x,
+                         idx_t, idx_i32, nt, M, K, hi, lo, u, inv_n, slab);
+    });
+  });
   PTV3_LAUNCH_CHECK();
   hipLaunchKernelGGL(sn_sk_finish_kernel, dim3((unsigned)cdiv(K, SN_FIN_COLS)), dim3(SN_THREADS), 0, st, slab, chunks, K,
                      A, u_next);
@@ -477,21 +470,16 @@ extern "C" int ptv3_sonata_ce_fwd(const void* x, int x_dtype, const void* idx_t,
   double* loss_m = (double*)workspace;
   const int64_t want = cdiv(M, SN_WAVES);
   const dim3 grid((unsigned)(want < 8192 ? want : 8192));
-#define SN_FWD(KPL)                                                                                                   \
-  if (x_dtype == PTV3_BF16 && s_dtype == PTV3_BF16)                                                                   \
-    hipLaunchKernelGGL((sn_ce_fwd_kernel<__bf16, __bf16, KPL>), grid, dim3(SN_THREADS), 0, st, (const __bf16*)x, idx_t, \
-                       idx_t_i32, nt, (const __bf16*)s, idx_s, idx_s_i32, ns, M, K, thi, tlo, shi, slo, u, loss_m, d, lse); \
-  else if (x_dtype == PTV3_BF16)                                                                                      \
-    hipLaunchKernelGGL((sn_ce_fwd_kernel<__bf16, float, KPL>), grid, dim3(SN_THREADS), 0, st, (const __bf16*)x, idx_t, \
-                       idx_t_i32, nt, (const float*)s, idx_s, idx_s_i32, ns, M, K, thi, tlo, shi, slo, u, loss_m, d, lse); \
-  else if (s_dtype == PTV3_BF16)                                                                                      \
-    hipLaunchKernelGGL((sn_ce_fwd_kernel<float, __bf16, KPL>), grid, dim3(SN_THREADS), 0, st, (const float*)x, idx_t,  \
-                       idx_t_i32, nt, (const __bf16*)s, idx_s, idx_s_i32, ns, M, K, thi, tlo, shi, slo, u, loss_m, d, lse); \
-  else                                                                                                                \
-    hipLaunchKernelGGL((sn_ce_fwd_kernel<float, float, KPL>), grid, dim3(SN_THREADS), 0, st, (const float*)x, idx_t,   \
-                       idx_t_i32, nt, (const float*)s, idx_s, idx_s_i32, ns, M, K, thi, tlo, shi, slo, u, loss_m, d, lse)
-  SN_BY_K(K, SN_FWD);
-#undef SN_FWD
+  by_dtype(x_dtype, [&](auto tx) {
+    using X = typename decltype(tx)::type;
+    by_dtype(s_dtype, [&](auto ts) {
+      using S = typename decltype(ts)::type;
+      by_value<2, 16, 64>(sn_kpl(K), [&](auto KPL) {
+        hipLaunchKernelGGL((sn_ce_fwd_kernel<X, S, KPL()>), grid, dim3(SN_THREADS), 0, st, (const X*)x, idx_t, idx_t_i32,
+                           nt, (const S*)s, idx_s, idx_s_i32, ns, M, K, thi, tlo, shi, slo, u, loss_m, d, lse);
+      });
+    });
+  });
   PTV3_LAUNCH_CHECK();
   hipLaunchKernelGGL(sn_ce_finish_kernel, dim3(1), dim3(SN_THREADS), 0, st, loss_m, idx_s, idx_s_i32, M, offset_s, nb,
                      loss, gscale);
@@ -514,25 +502,17 @@ extern "C" int ptv3_sonata_ce_bwd(const float* dloss, const void* x, int x_dtype
   sn_split(inv_tau, &shi, &slo);
   const int64_t want = cdiv(ns, SN_WAVES);
   const dim3 grid((unsigned)(want < 8192 ? want : 8192));
-#define SN_BWD(KPL)                                                                                                   \
-  if (x_dtype == PTV3_BF16 && s_dtype == PTV3_BF16)                                                                   \
-    hipLaunchKernelGGL((sn_ce_bwd_kernel<__bf16, __bf16, KPL>), grid, dim3(SN_THREADS), 0, st, dloss, (const __bf16*)x, \
-                       idx_t, idx_t_i32, nt, (const __bf16*)s, idx_s, idx_s_i32, ns, M, K, thi, tlo, shi, slo, u, d, lse, \
-                       offset_s, nb, gscale, (__bf16*)ds);                                                            \
-  else if (x_dtype == PTV3_BF16)                                                                                      \
-    hipLaunchKernelGGL((sn_ce_bwd_kernel<__bf16, float, KPL>), grid, dim3(SN_THREADS), 0, st, dloss, (const __bf16*)x, \
-                       idx_t, idx_t_i32, nt, (const float*)s, idx_s, idx_s_i32, ns, M, K, thi, tlo, shi, slo, u, d, lse, \
-                       offset_s, nb, gscale, (float*)ds);                                                             \
-  else if (s_dtype == PTV3_BF16)                                                                                      \
-    hipLaunchKernelGGL((sn_ce_bwd_kernel<float, __bf16, KPL>), grid, dim3(SN_THREADS), 0, st, dloss, (const float*)x,  \
-                       idx_t, idx_t_i32, nt, (const __bf16*)s, idx_s, idx_s_i32, ns, M, K, thi, tlo, shi, slo, u, d, lse, \
-                       offset_s, nb, gscale, (__bf16*)ds);                                                            \
-  else                                                                                                                \
-    hipLaunchKernelGGL((sn_ce_bwd_kernel<float, float, KPL>), grid, dim3(SN_THREADS), 0, st, dloss, (const float*)x,   \
-                       idx_t, idx_t_i32, nt, (const float*)s, idx_s, idx_s_i32, ns, M, K, thi, tlo, shi, slo, u, d, lse, \
-                       offset_s, nb, gscale, (float*)ds)
-  SN_BY_K(K, SN_BWD);
-#undef SN_BWD
+  by_dtype(x_dtype, [&](auto tx) {
+    using X = typename decltype(tx)::type;
+    by_dtype(s_dtype, [&](auto ts) {
+      using S = typename decltype(ts)::type;
+      by_value<2, 16, 64>(sn_kpl(K), [&](auto KPL) {
+        hipLaunchKernelGGL((sn_ce_bwd_kernel<X, S, KPL()>), grid, dim3(SN_THREADS), 0, st, dloss, (const X*)x, idx_t,
+                           idx_t_i32, nt, (const S*)s, idx_s, idx_s_i32, ns, M, K, thi, tlo, shi, slo, u, d, lse, offset_s,
+                           nb, gscale, (S*)ds);
+      });
+    });
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }

@@ -468,12 +468,9 @@ extern "C" int ptv3_subm_neighbors_blocks(const int32_t* indices, int64_t n, con
   // sites per workgroup: several independent payload reads per lane and a wave or more of block lookups; measured
   // flat around these at 100k sites (5^3: 40.0 / 34.2 / 33.5 / 36.4 us at 4 / 8 / 16 / 32 sites; 3^3: 12.3 / 12.1 /
   // 13.4 / 16.2 us at 16 / 32 / 64 / 128), the smaller choice keeps the deeper levels' few thousand sites spread out
-  switch (ksize) {
-    case 1: bt_neighbors_launch<1, 256>(indices, n, t, nbr, s); break;
-    case 3: bt_neighbors_launch<3, 16>(indices, n, t, nbr, s); break;
-    case 5: bt_neighbors_launch<5, 16>(indices, n, t, nbr, s); break;
-    default: bt_neighbors_launch<7, 4>(indices, n, t, nbr, s); break;
-  }
+  by_value<1, 3, 5, 7>(ksize, [&](auto K) {
+    bt_neighbors_launch<K(), K() == 1 ? 256 : K() == 7 ? 4 : 16>(indices, n, t, nbr, s);
+  });
   PTV3_LAUNCH_CHECK();
   return PTV3_OK;
 }

@@ -218,26 +218,24 @@ template <typename T, int D>
 static int dispatch_axes(int S, const void* q, const void* k, const void* v, const float* qt, const float* kt,
                          const float* vt, const SwinTables& tab, const long long* n2n, const int* w_start, int nwin,
                          const float* crse, void* out, int heads, int max_tokens, hipStream_t s) {
-  switch (S) {
-    case 3: return launch_swin<T, D, 3>(q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);
-    case 6: return launch_swin<T, D, 6>(q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);
-    case 9: return launch_swin<T, D, 9>(q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);
-  }
-  set_error("swin_attn: %d signal axes (3, 6 or 9: XYZ, XYZ_RGB, XYZ_RGB_NORM)", S);
-  return PTV3_ERR_UNSUPPORTED;
+  int rc = PTV3_ERR_UNSUPPORTED;
+  const bool known = by_value<3, 6, 9>(S, [&](auto SV) {
+    rc = launch_swin<T, D, SV()>(q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);
+  });
+  if (!known) set_error("swin_attn: %d signal axes (3, 6 or 9: XYZ, XYZ_RGB, XYZ_RGB_NORM)", S);
+  return rc;
 }
 
 template <typename T>
 static int dispatch_dim(int D, int S, const void* q, const void* k, const void* v, const float* qt, const float* kt,
                         const float* vt, const SwinTables& tab, const long long* n2n, const int* w_start, int nwin,
                         const float* crse, void* out, int heads, int max_tokens, hipStream_t s) {
-  switch (D) {
-    case 8: return dispatch_axes<T, 8>(S, q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);
-    case 16: return dispatch_axes<T, 16>(S, q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);
-    case 32: return dispatch_axes<T, 32>(S, q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);
-  }
-  set_error("swin_attn: head_dim %d (8, 16 or 32)", D);
-  return PTV3_ERR_UNSUPPORTED;
+  int rc = PTV3_ERR_UNSUPPORTED;
+  const bool known = by_value<8, 16, 32>(D, [&](auto DV) {
+    rc = dispatch_axes<T, DV()>(S, q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);
+  });
+  if (!known) set_error("swin_attn: head_dim %d (8, 16 or 32)", D);
+  return rc;
 }
 
 }  // namespace ptv3
@@ -286,7 +284,7 @@ extern "C" int ptv3_swin_attn_fwd(const void* q, const void* k, const void* v, c
   hipStream_t s = (hipStream_t)stream;
   // algorithmic work: (1 + 3 S) 2 D flops per (query, key) pair and head - the pair count lives in w_start on the
   // device; a caller that knows it says so through ptv3_profile_hint_flops - and q, k, v, out once each
-  const int esz = dtype == PTV3_F32 ? 4 : 2;
+  const int esz = dtype_bytes(dtype);
   const int prof = prof_begin(s, PROF_WINDOW_ATTN, 0.0, 4.0 * (double)n * heads * head_dim * esz + 12.0 * n, nullptr, 0, 0.0);
   prof_kernel(prof, PK_SWIN_ATTN);
   // table products on the matrix core (swin_attn_mfma.hip) unless switched off or the window does not fit its LDS plan
@@ -298,12 +296,13 @@ extern "C" int ptv3_swin_attn_fwd(const void* q, const void* k, const void* v, c
                         (const long long*)n2n, w_start, num_windows, n_crse, out, heads, max_tokens, s);
   if (rc != -1) {
     prof_kernel(prof, PK_SWIN_ATTN_MFMA);
-  } else if (dtype == PTV3_F32)
-    rc = dispatch_dim<float>(head_dim, num_axes, q, k, v, q_table, k_table, v_table, tab, (const long long*)n2n,
-                             w_start, num_windows, n_crse, out, heads, max_tokens, s);
-  else
-    rc = dispatch_dim<__bf16>(head_dim, num_axes, q, k, v, q_table, k_table, v_table, tab, (const long long*)n2n,
-                              w_start, num_windows, n_crse, out, heads, max_tokens, s);
+  } else {
+    by_dtype(dtype, [&](auto t) {
+      rc = dispatch_dim<typename decltype(t)::type>(head_dim, num_axes, q, k, v, q_table, k_table, v_table, tab,
+                                                    (const long long*)n2n, w_start, num_windows, n_crse, out, heads,
+                                                    max_tokens, s);
+    });
+  }
   prof_end(prof, s);
   return rc;
 }

@@ -264,24 +264,18 @@ static int launch_bwd(const void* q, const void* k, const void* v, const void* d
 
 template <typename T, int D, typename... A>
 static int bwd_axes(int S, A... a) {
-  switch (S) {
-    case 3: return launch_bwd<T, D, 3>(a...);
-    case 6: return launch_bwd<T, D, 6>(a...);
-    case 9: return launch_bwd<T, D, 9>(a...);
-  }
-  set_error("swin_attn_bwd: %d signal axes (3, 6 or 9)", S);
-  return PTV3_ERR_UNSUPPORTED;
+  int rc = PTV3_ERR_UNSUPPORTED;
+  if (!by_value<3, 6, 9>(S, [&](auto SV) { rc = launch_bwd<T, D, SV()>(a...); }))
+    set_error("swin_attn_bwd: %d signal axes (3, 6 or 9)", S);
+  return rc;
 }
 
 template <typename T, typename... A>
 static int bwd_dim(int D, int S, A... a) {
-  switch (D) {
-    case 8: return bwd_axes<T, 8>(S, a...);
-    case 16: return bwd_axes<T, 16>(S, a...);
-    case 32: return bwd_axes<T, 32>(S, a...);
-  }
-  set_error("swin_attn_bwd: head_dim %d (8, 16 or 32)", D);
-  return PTV3_ERR_UNSUPPORTED;
+  int rc = PTV3_ERR_UNSUPPORTED;
+  if (!by_value<8, 16, 32>(D, [&](auto DV) { rc = bwd_axes<T, DV()>(S, a...); }))
+    set_error("swin_attn_bwd: head_dim %d (8, 16 or 32)", D);
+  return rc;
 }
 
 }  // namespace ptv3
@@ -320,9 +314,11 @@ extern "C" int ptv3_swin_attn_bwd(const void* q, const void* k, const void* v, c
     }
   if (num_windows <= 0 || n <= 0) return PTV3_OK;
   const long long* nn = (const long long*)n2n;
-  if (dtype == PTV3_F32)
-    return bwd_dim<float>(head_dim, num_axes, q, k, v, dout, q_table, k_table, v_table, tab, nn, w_start, num_windows,
-                          n_crse, dq, dk, dv, dq_table, dk_table, dv_table, heads, max_tokens, s);
-  return bwd_dim<__bf16>(head_dim, num_axes, q, k, v, dout, q_table, k_table, v_table, tab, nn, w_start, num_windows,
-                         n_crse, dq, dk, dv, dq_table, dk_table, dv_table, heads, max_tokens, s);
+  int rc = PTV3_OK;
+  by_dtype(dtype, [&](auto t) {
+    rc = bwd_dim<typename decltype(t)::type>(head_dim, num_axes, q, k, v, dout, q_table, k_table, v_table, tab, nn, w_start,
+                                             num_windows, n_crse, dq, dk, dv, dq_table, dk_table, dv_table, heads,
+                                             max_tokens, s);
+  });
+  return rc;
 }

@@ -341,12 +341,11 @@ template <typename T, int D>
 static int swm_axes(int S, const void* q, const void* k, const void* v, const float* qt, const float* kt, const float* vt,
                     const SwinTablesM& tab, const long long* n2n, const int* w_start, int nwin, const float* crse,
                     void* out, int heads, int max_tokens, hipStream_t s) {
-  switch (S) {
-    case 3: return launch_swm<T, D, 3>(q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);
-    case 6: return launch_swm<T, D, 6>(q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);
-    case 9: return launch_swm<T, D, 9>(q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);
-  }
-  return -1;
+  int rc = -1;
+  by_value<3, 6, 9>(S, [&](auto SV) {
+    rc = launch_swm<T, D, SV()>(q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);
+  });
+  return rc;
 }
 
 // -1: shape not served by this kernel (the caller falls back to swin_attn_kernel); otherwise a PTV3_* status
@@ -355,15 +354,14 @@ int swin_attn_mfma(int dtype, int D, int S, const void* q, const void* k, const 
                    int nwin, const float* crse, void* out, int heads, int max_tokens, hipStream_t s) {
   SwinTablesM tab;
   for (int c = 0; c < SWM_MAX_AXES; ++c) { tab.start[c] = start[c]; tab.rows[c] = rows[c]; }
-#define SWM_DIM(T)                                                                                                  \
-  switch (D) {                                                                                                      \
-    case 8: return swm_axes<T, 8>(S, q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);   \
-    case 16: return swm_axes<T, 16>(S, q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s); \
-    case 32: return swm_axes<T, 32>(S, q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s); \
-    default: return -1;                                                                                             \
-  }
-  if (dtype == PTV3_F32) { SWM_DIM(float) } else { SWM_DIM(__bf16) }
-#undef SWM_DIM
+  int rc = -1;
+  by_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    by_value<8, 16, 32>(D, [&](auto DV) {
+      rc = swm_axes<T, DV()>(S, q, k, v, qt, kt, vt, tab, n2n, w_start, nwin, crse, out, heads, max_tokens, s);
+    });
+  });
+  return rc;
 }
 
 }  // namespace ptv3

@@ -4,7 +4,6 @@
 // window_attn_backward; a new argument of the operation is added here, in window_attn_validate, in the entry that
 // exposes it and in ops._attn_check on the Python side.
 #pragma once
-#include <type_traits>
 #include "common.h"
 #include "../../include/ptv3_hip.h"
 
@@ -74,18 +73,13 @@ int window_attn_validate(WindowAttnCall& a, const WindowAttnSpec& spec, bool bac
 int window_attn_forward(WindowAttnCall& a, const WindowAttnSpec& spec);
 int window_attn_backward(WindowAttnCall& a, const WindowAttnSpec& spec);
 
-// (dtype, head_dim) -> f(WaType<T>{}, std::integral_constant<int, head_dim / 16>{}); validated calls only
-template <typename T> struct WaType { using type = T; };
+// (dtype, head_dim) -> f(TypeTag<T>{}, std::integral_constant<int, head_dim / 16>{}); validated calls only
 template <typename F> inline int window_attn_dispatch(int dtype, int head_dim, F&& f) {
-  auto by_dim = [&](auto t) {
-    switch (head_dim) {
-      case 16: return f(t, std::integral_constant<int, 1>{});
-      case 32: return f(t, std::integral_constant<int, 2>{});
-      case 64: return f(t, std::integral_constant<int, 4>{});
-      default: return (int)PTV3_ERR_UNSUPPORTED;
-    }
-  };
-  return dtype == PTV3_F32 ? by_dim(WaType<float>{}) : by_dim(WaType<__bf16>{});
+  int rc = PTV3_ERR_UNSUPPORTED;
+  by_dtype(dtype, [&](auto t) {
+    by_value<16, 32, 64>(head_dim, [&](auto HD) { rc = f(t, std::integral_constant<int, HD() / 16>{}); });
+  });
+  return rc;
 }
 
 }  // namespace ptv3

@@ -617,9 +617,7 @@ static void launch_full(const FullArgs<T>& a) {
 
 template <typename T, int ND, int QT>
 static void launch_full_rpe(const FullArgs<T>& a, int rpe_mode) {
-  if (rpe_mode == 2) launch_full<T, ND, 2, QT>(a);
-  else if (rpe_mode == 1) launch_full<T, ND, 1, QT>(a);
-  else launch_full<T, ND, 0, QT>(a);
+  by_value<0, 1, 2>(rpe_mode, [&](auto RPE) { launch_full<T, ND, RPE(), QT>(a); });
 }
 
 static void full_config(int64_t pairs, int K, int qt_max, size_t lds, int* waves_out, int* qt_out) {
@@ -752,7 +750,7 @@ int window_attn_forward(WindowAttnCall& a, const WindowAttnSpec& spec) {
   bool empty;
   const int ok = window_attn_validate(a, spec, false, &empty);
   if (ok != PTV3_OK || empty) return ok;
-  const int esz = a.dtype == PTV3_F32 ? 4 : 2;
+  const int esz = dtype_bytes(a.dtype);
   // algorithmic work: 4 * sum_w len_w^2 * c flops; qkv read + out write + the two index maps (+ the
   // voxel coordinates of the RPE table lookup)
   const double len_sq = a.cu_seqlens && a.sum_len_sq > 0 ? a.sum_len_sq : (double)a.n_pad * a.patch;

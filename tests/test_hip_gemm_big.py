@@ -169,3 +169,37 @@ def test_sparse_conv_split_k_through_the_256_point_tile(dev, dtype, n, c):
     ref = torch.relu(O.subm_conv3d(xd.float().cpu(), idx, wd.float().cpu().reshape(w.shape), bias))
     tol = 1e-4 if dtype == torch.float32 else 2.0 ** -6
     assert (o1.float().cpu() - ref).abs().max().item() < tol * max(1.0, ref.abs().max().item())
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("env,n,cin,cout", [
+    ({"PTV3_CONV_TILE": "2", "PTV3_CONV_STAGES": "4"}, 300, 128, 136),     # conv_tile_kernel<T, 128, 64, 4>
+    ({"PTV3_CONV_TILE": "2", "PTV3_CONV_STAGES": "4"}, 257, 64, 256),      # bf16: <__bf16, 256, 64, 4>
+    ({"PTV3_CONV_TILE": "0", "PTV3_GEMM_BIG": "0", "PTV3_GEMM_SPLITK": "0", "PTV3_GEMM_PD": "2"}, 260, 64, 72),   # gemm_kernel<T, 4, true, 2>
+    ({"PTV3_CONV_TILE": "0", "PTV3_GEMM_BIG": "0", "PTV3_GEMM_SPLITK": "0", "PTV3_GEMM_PD": "1"}, 260, 64, 72),   # <T, 4, true, 1>
+], ids=["ring4_bn128", "ring4_bn256", "pd2", "pd1"])
+def test_sparse_conv_launch_variants_chosen_by_environment(dev, dtype, env, n, cin, cout):
+    """The instantiations of ptv3_gemm's ladders that only an environment switch selects (read per call): the four-stage
+    ring of conv_tile_kernel and the register-ring depths 2 and 1 of gemm_kernel at 64 output channels per tile, against
+    the conv restatement at this file's tolerance."""
+    from ptv3_hip import ops
+    import ptv3_scenes as S
+    from oracle import ptv3 as O
+    sc = S.make_scene(n, 4, 24, seed=n)
+    idx = torch.cat([torch.zeros(n, 1, dtype=torch.int32), torch.from_numpy(sc["grid_coord"]).int()], 1).contiguous()
+    g = torch.Generator().manual_seed(n + cout)
+    feat = torch.randn(n, cin, generator=g)
+    w = torch.randn(cout, 3, 3, 3, cin, generator=g) / (27 * cin) ** 0.5
+    bias = torch.randn(cout, generator=g)
+    nbr, _ = ops.subm_neighbors(idx.to(dev), 3)
+    order = torch.randperm(n, generator=g).int().to(dev)
+    xd, wd = feat.to(dev, dtype), w.reshape(cout, -1).to(dev, dtype).contiguous()
+    os.environ.update(env)
+    try:
+        out = ops.gemm(xd, wd, bias=bias.to(dev), nbr=nbr, kvol=27, row_order=order, act=ops.ACT_RELU)
+    finally:
+        for k in env:
+            os.environ.pop(k, None)
+    ref = torch.relu(O.subm_conv3d(xd.float().cpu(), idx, wd.float().cpu().reshape(w.shape), bias))
+    tol = 1e-4 if dtype == torch.float32 else 2.0 ** -6
+    assert (out.float().cpu() - ref).abs().max().item() < tol * max(1.0, ref.abs().max().item())
