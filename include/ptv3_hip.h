@@ -1378,6 +1378,45 @@ int ptv3_concerto_cos_fwd(const void* a, int a_dtype, const void* b, int b_dtype
 int ptv3_concerto_cos_bwd(const float* dloss, const void* a, int a_dtype, const void* b, int b_dtype,
                           const int64_t* patch_ids, int64_t U, int64_t nb, int D, int shift, void* da, void* stream);
 
+/* ---- validation hooks: SemSegEvaluator / ClsEvaluator / InsSegEvaluator (csrc/evaluator.hip) -------------------------
+ * Element types of the arrays these two entry points dispatch over, beside PTV3_F32 / PTV3_BF16. */
+#define PTV3_F16 2
+#define PTV3_I32 3
+#define PTV3_I64 4
+#define PTV3_U8 5 /* torch.uint8 and torch.bool */
+/* ptv3_seg_confusion: output.max(1)[1], pred[inverse] and intersection_and_union_gpu of the reference's
+ *   pointcept/engines/hooks/evaluator.py:39-46 / :141-152 and pointcept/utils/misc.py:53-65 as one counting pass.
+ *   src is either logits (n, K) in PTV3_F32 / PTV3_BF16 / PTV3_F16 - the prediction of a row is then the LOWEST index
+ *   among its maxima; a row with a NaN is out of contract - or the prediction (n) itself in PTV3_I32 / PTV3_I64.  target
+ *   (m) PTV3_I32 / PTV3_I64.  With inverse (m) int64, element e is predicted by row inverse[e] (an entry outside [0, n) is
+ *   counted nowhere); without it m == n.  Logits WITH an inverse take pred_ws (n) int32, else it may be NULL.
+ *   counts (3, K) int64 = intersection, predicted area, target area, ADDED to what is there (union = predicted + target -
+ *   intersection is the caller's).  An element whose target equals ignore_index takes ignore_index as its prediction; a
+ *   value outside [0, K) falls in no bin of any of the three: the histc(bins=K, min=0, max=K-1) calls over integers.
+ *   1 <= K <= PTV3_SEG_CONFUSION_MAX_K (the 3K-bin histogram lives in LDS); n, m < 2^31.  Integer atomics: bitwise equal
+ *   from run to run.
+ * ptv3_insseg_associate: the body of InsSegEvaluator.associate_instances (evaluator.py:309-341) for one scene, without
+ *   the gathered copy of :577.  masks (P, nm) PTV3_I32 / PTV3_U8 / PTV3_I64, an entry is SET when != 0 (:317).  code (n)
+ *   int32 per evaluated point: bits 0-30 the compact index of the point's counted ground-truth instance in [0, G), or G
+ *   for none (a larger value is counted in no column); bit 31 set when the point's segment is ignored (void).
+ *   col_start NULL: the evaluated cloud is the masks' own, n == nm, point j is column j.  col_start (nm + 1) int32: the
+ *   evaluated cloud is another one (the nearest-neighbour map of :569-576, inverted by the caller): the points that read
+ *   column j are col_start[j] .. col_start[j + 1] - 1 and `code` is stored in that order; a range is clipped to [0, n].
+ *   Either way a row of masks is read once, in order.  Outputs, all int32 and all OVERWRITTEN: inter (P, G + 1)[p, g] =
+ *   evaluated points of code g on set entries of p (:327-331), vert_count (P) = evaluated points on set entries (:318),
+ *   void_inter (P) = those of them that are void (:319-321).  0 <= G <= PTV3_INSSEG_MAX_GT (the row's histogram lives in
+ *   LDS); a row is cut into chunks of ptv3_insseg_chunk() entries, one workgroup each, and the result does not depend
+ *   on the cut.  P == 0 or n == 0 launches nothing. */
+#define PTV3_SEG_CONFUSION_MAX_K 1024
+#define PTV3_INSSEG_MAX_GT 4095
+int ptv3_seg_confusion(const void* src, int src_dtype, int64_t n, const int64_t* inverse, const void* target,
+                       int target_dtype, int64_t m, int K, int64_t ignore_index, int64_t* counts, int32_t* pred_ws,
+                       void* stream);
+int ptv3_insseg_chunk(void);
+int ptv3_insseg_associate(const void* masks, int mask_dtype, int64_t P, int64_t nm, const int32_t* col_start,
+                          const int32_t* code, int64_t n, int G, int32_t* inter, int32_t* vert_count, int32_t* void_inter,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

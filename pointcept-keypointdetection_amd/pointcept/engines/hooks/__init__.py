@@ -29,3 +29,4 @@ class HookBase:
 from .keypoint_evaluator import KeypointEvaluator  # noqa: E402,F401
 from .offset_keypoint_evaluator import OffsetKeypointEvaluator  # noqa: E402,F401
 from .default import ModelHook  # noqa: E402,F401
+from .evaluator import ClsEvaluator, SemSegEvaluator, InsSegEvaluator  # noqa: E402,F401

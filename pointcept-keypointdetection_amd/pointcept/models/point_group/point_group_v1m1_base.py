@@ -4,7 +4,7 @@ Constructor keywords, state_dict and the returned keys are the reference's.  The
 BatchNorm kernels.  The evaluation tail (:101-178) - ball query, copy of the neighbour lists, host search, dense mask
 scatter, one masked mean and one copy per proposal - is ptv3_pg_cluster + ptv3_pg_proposals on the device (DESIGN.md
 section 22): one read-back of a four-integer record decides the output shapes, and the three results are copied to the
-host at the end because the reference returns CPU tensors.  When a point has more than 1000 neighbours the lists the
+host at the end because the reference returns CPU tensors (set_device_results(True) leaves them on the device).  When a point has more than 1000 neighbours the lists the
 reference searches are cut and its graph is directed; clustering then takes the list path (pointgroup_ops), which
 reproduces that search.  In training the two bias losses (:75-89) are one forward and one backward launch
 (ptv3_pg_bias_loss_fwd / _bwd).  set_fused(False) takes the list path always and composes the bias losses in torch.
@@ -48,6 +48,13 @@ class PointGroupBase(nn.Module):
         )
         self.seg_head = Linear(backbone_out_channels, semantic_num_classes)
         self._fused = True
+        self._device_results = False
+
+    def set_device_results(self, on=True):
+        """True: eval leaves pred_scores / pred_masks / pred_classes on the device (InsSegEvaluator reads them there);
+        the default returns CPU tensors, as the reference does."""
+        self._device_results = bool(on)
+        return self
 
     def set_fused(self, on=True):
         """False: cluster through pointgroup_ops' lists and host search (the composition the reference runs)."""
@@ -122,6 +129,8 @@ class PointGroupBase(nn.Module):
                         pred_classes=torch.tensor([]))
         classes, scores, masks = ops.pg_proposals(idxs.contiguous(), offs.contiguous(), prob, segment_pred,
                                                   self.cluster_propose_points, large, row_map=rows)
+        if self._device_results:
+            return dict(pred_scores=scores, pred_masks=masks, pred_classes=classes)
         return dict(pred_scores=scores.cpu(), pred_masks=masks.cpu(), pred_classes=classes.cpu())
 
     def forward(self, data_dict):

@@ -3095,3 +3095,147 @@ def pg_bias_loss_bwd(dloss, bias_pred, coord, centroid, instance, fwd_out, ignor
                                         int(ignore_index), bias_pred.shape[0], _p(fwd_out), _p(dbias), _stream()),
               "ptv3_pg_bias_loss_bwd")
     return dbias
+
+
+# ---------------------------------------------------------------------------------------------
+# validation hooks (csrc/evaluator.hip)
+from .lib import PTV3_F16, PTV3_I32, PTV3_I64, PTV3_U8  # noqa: E402
+from .lib import PTV3_SEG_CONFUSION_MAX_K as SEG_CONFUSION_MAX_K, PTV3_INSSEG_MAX_GT as INSSEG_MAX_GT  # noqa: E402
+
+_EV_LOGITS = {torch.float32: PTV3_F32, torch.bfloat16: PTV3_BF16, torch.float16: PTV3_F16}
+_EV_INT = {torch.int32: PTV3_I32, torch.int64: PTV3_I64}
+_EV_MASK = {torch.int32: PTV3_I32, torch.int64: PTV3_I64, torch.uint8: PTV3_U8, torch.bool: PTV3_U8}
+INSSEG_VOID = -2 ** 31        # bit 31 of a code: the point's segment is ignored
+
+
+def insseg_chunk():
+    """Points of one proposal that one workgroup of ptv3_insseg_associate counts."""
+    return int(lib.ptv3_insseg_chunk())
+
+
+def _seg_confusion_args(src, target, k, inverse, counts):
+    k = int(k)
+    if k < 1:
+        raise RuntimeError(f"seg_confusion: {k} classes")
+    if src.dim() == 2:
+        if src.dtype not in _EV_LOGITS or src.shape[1] != k:
+            raise TypeError(f"seg_confusion: logits {tuple(src.shape)} {src.dtype}, expected (N, {k}) fp32 / bf16 / fp16")
+    elif src.dim() != 1 or src.dtype not in _EV_INT:
+        raise TypeError(f"seg_confusion: src {tuple(src.shape)} {src.dtype}: logits (N, K) or a prediction (N) int32 / "
+                        "int64")
+    if target.dim() != 1 or target.dtype not in _EV_INT:
+        raise TypeError(f"seg_confusion: target {tuple(target.shape)} {target.dtype}, expected (M) int32 / int64")
+    if inverse is not None and (inverse.dim() != 1 or inverse.dtype != torch.int64
+                                or inverse.shape[0] != target.shape[0]):
+        raise TypeError("seg_confusion: inverse must be int64 with one entry per target")
+    if inverse is None and target.shape[0] != src.shape[0]:
+        raise RuntimeError(f"seg_confusion: {src.shape[0]} rows, {target.shape[0]} targets and no inverse")
+    if counts is not None and (counts.dtype != torch.int64 or tuple(counts.shape) != (3, k)
+                               or counts.device != src.device):
+        raise TypeError(f"seg_confusion: counts must be (3, {k}) int64 on the inputs' device")
+    return k
+
+
+def seg_confusion_torch(src, target, k, ignore_index=-1, inverse=None, counts=None):
+    """What seg_confusion counts, composed in torch on the inputs' device (any device): evaluator.py:141-152 with
+    misc.py:53-65, the three histograms as bincounts with a spare bin for the values outside [0, K)."""
+    k = _seg_confusion_args(src, target, k, inverse, counts)
+    if src.dim() == 2:
+        cls = torch.arange(k, device=src.device).expand_as(src)
+        pred = torch.where(src == src.max(1, keepdim=True)[0], cls, k).min(1)[0]   # lowest index among the maxima
+    else:
+        pred = src.long()
+    if inverse is not None:
+        pred = pred[inverse]
+    tgt = target.long()
+    pred = torch.where(tgt == ignore_index, torch.full_like(pred, int(ignore_index)), pred)
+
+    def hist(x):
+        return torch.bincount(torch.where((x >= 0) & (x < k), x, k), minlength=k + 1)[:k]
+
+    out = torch.stack([hist(torch.where(pred == tgt, pred, -1)), hist(pred), hist(tgt)])
+    if counts is None:
+        return out
+    return counts.add_(out)
+
+
+def seg_confusion(src, target, k, ignore_index=-1, inverse=None, counts=None):
+    """ptv3_seg_confusion: counts (3, K) int64 = intersection, predicted area and target area of src - logits (N, K)
+    fp32 / bf16 / fp16 or a prediction (N) int32 / int64 - against target (M) int32 / int64, through inverse (M) int64
+    when given; added to `counts` when given.  Above SEG_CONFUSION_MAX_K classes the same counts are composed in torch."""
+    for t, name in ((src, "src"), (target, "target"), (inverse, "inverse"), (counts, "counts")):
+        _chk(t, f"seg_confusion: {name}")
+    k = _seg_confusion_args(src, target, k, inverse, counts)
+    if k > SEG_CONFUSION_MAX_K:
+        return seg_confusion_torch(src, target, k, ignore_index, inverse, counts)
+    if counts is None:
+        counts = torch.zeros((3, k), dtype=torch.int64, device=src.device)
+    n, m = src.shape[0], target.shape[0]
+    logits = src.dim() == 2
+    pred_ws = torch.empty(n, dtype=torch.int32, device=src.device) if logits and inverse is not None else None
+    lib.check(lib.ptv3_seg_confusion(_p(src), (_EV_LOGITS if logits else _EV_INT)[src.dtype], n, _p(inverse), _p(target),
+                                     _EV_INT[target.dtype], m, k, int(ignore_index), _p(counts), _p(pred_ws), _stream()),
+              "ptv3_seg_confusion")
+    return counts
+
+
+def _insseg_args(masks, code, g, idx):
+    g = int(g)
+    if masks.dim() != 2 or masks.dtype not in _EV_MASK:
+        raise TypeError(f"insseg_associate: masks {tuple(masks.shape)} {masks.dtype}, expected (P, N) int32 / uint8 / "
+                        "bool / int64")
+    if code.dim() != 1 or code.dtype != torch.int32:
+        raise TypeError("insseg_associate: code must be (N) int32")
+    if idx is not None and (idx.dim() != 1 or idx.dtype not in _EV_INT or idx.shape[0] != code.shape[0]):
+        raise TypeError("insseg_associate: idx must be int32 / int64 with one entry per code")
+    if idx is None and masks.shape[1] != code.shape[0]:
+        raise RuntimeError(f"insseg_associate: masks of {masks.shape[1]} points, {code.shape[0]} codes and no idx")
+    if g < 0:
+        raise RuntimeError(f"insseg_associate: {g} ground-truth instances")
+    return g
+
+
+def insseg_associate_torch(masks, code, g, idx=None):
+    """What insseg_associate counts, composed in torch on the inputs' device (any device): the set mask, gathered through
+    idx, added into the columns of inter by index_add_."""
+    g = _insseg_args(masks, code, g, idx)
+    on = masks.ne(0)
+    if idx is not None:
+        on = on[:, idx.long()]
+    p = on.shape[0]
+    inter = torch.zeros((p, g + 1), dtype=torch.int32, device=masks.device)
+    if on.numel():
+        inter.index_add_(1, (code & 0x7FFFFFFF).long(), on.to(torch.int32))
+    vert = on.sum(1, dtype=torch.int32)
+    void = (on & (code < 0)[None]).sum(1, dtype=torch.int32)
+    return inter, vert, void
+
+
+def insseg_associate(masks, code, g, idx=None):
+    """ptv3_insseg_associate: (inter (P, G + 1), vert_count (P), void_inter (P)), all int32, of masks (P, Nm) against the
+    per-point codes (N) int32 (compact ground-truth index or G, INSSEG_VOID added on a void point).  With idx (N) int32 /
+    int64, evaluated point i reads masks[:, idx[i]] (an entry outside [0, Nm) is not set): the map is inverted here, by
+    one sort, into the points of every mask column, so that the kernel reads each row once and in order instead of
+    gathering from it.  Above INSSEG_MAX_GT instances the same tables are composed in torch."""
+    for t, name in ((masks, "masks"), (code, "code"), (idx, "idx")):
+        _chk(t, f"insseg_associate: {name}")
+    g = _insseg_args(masks, code, g, idx)
+    if g > INSSEG_MAX_GT:
+        return insseg_associate_torch(masks, code, g, idx)
+    p, nm = masks.shape
+    n = code.shape[0]
+    dev = masks.device
+    if p == 0 or n == 0:
+        return (torch.zeros((p, g + 1), dtype=torch.int32, device=dev), torch.zeros(p, dtype=torch.int32, device=dev),
+                torch.zeros(p, dtype=torch.int32, device=dev))
+    col_start = None
+    if idx is not None:
+        by_column, order = torch.sort(idx)
+        code = code[order]
+        col_start = torch.searchsorted(by_column, torch.arange(nm + 1, device=dev, dtype=idx.dtype)).int()
+    inter = torch.empty((p, g + 1), dtype=torch.int32, device=dev)
+    vert = torch.empty(p, dtype=torch.int32, device=dev)
+    void = torch.empty(p, dtype=torch.int32, device=dev)
+    lib.check(lib.ptv3_insseg_associate(_p(masks), _EV_MASK[masks.dtype], p, nm, _p(col_start), _p(code), n, g, _p(inter),
+                                        _p(vert), _p(void), _stream()), "ptv3_insseg_associate")
+    return inter, vert, void
