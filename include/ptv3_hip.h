@@ -1417,6 +1417,38 @@ int ptv3_insseg_associate(const void* masks, int mask_dtype, int64_t P, int64_t 
                           const int32_t* code, int64_t n, int G, int32_t* inter, int32_t* vert_count, int32_t* void_inter,
                           void* stream);
 
+/* Modulation of every PDBatchNorm of "SpUNet-v1m3" at once (csrc/pdnorm.hip, DESIGN.md section 28;
+ * pointcept/models/sparse_unet/spconv_unet_v1m3_pdnorm.py:63-74).  With a = SiLU(context) (Cc), layer l of width C_l has
+ * W_l (2 C_l, Cc) and b_l (2 C_l), row-major fp32: rows [0, C_l) give shift, rows [C_l, 2 C_l) give scale (the order of
+ * .chunk(2, dim=1)); gamma_l / beta_l (C_l) are the affine parameters of the active BatchNorm, NULL for 1 and 0.
+ * `table` is a DEVICE array of L rows of PTV3_PDNORM_ROW int64 - the addresses of W_l, b_l, gamma_l, beta_l and the
+ * active BatchNorm's running mean and variance (0 for NULL), then off_l = C_0 + .. + C_{l-1} and C_l; `widths` is the HOST
+ * array of the same C_l, which is what is checked before anything is launched (the host never reads the device table).
+ * Outputs are packed over sum(C_l) in layer order.
+ * ptv3_pdnorm_fwd, one launch: scale = W[C:] a + b[C:], shift = W[:C] a + b[:C];
+ *   fold == 0: out0 = gamma (1 + scale), out1 = beta (1 + scale) + shift - the weight / bias of a BatchNorm that
+ *     computes BN_affine(x) (1 + scale) + shift; one_plus (or NULL) receives 1 + scale for the backward.
+ *   fold != 0: additionally reads mean / var of the table (must not be NULL: the caller passes has_stats = 1 to say
+ *     so) and writes out0 = s = gamma (1 + scale) / sqrt(var + eps), out1 = t = beta (1 + scale) + shift - mean s: the
+ *     (bn_scale, bn_shift) pair of the conv epilogues.
+ * ptv3_pdnorm_bwd, two launches (the second sums the slabs): from d_out0 = d gamma_eff, d_out1 = d beta_eff (packed)
+ *   dshift = d_out1, dscale = d_out0 gamma + d_out1 beta, dgamma = d_out0 (1 + scale), dbeta = d_out1 (1 + scale)
+ *   (dgamma / dbeta may be NULL), db (2 sum C) with layer l at 2 off_l = [dshift; dscale], dW (2 sum C, Cc) with layer l
+ *   at row 2 off_l = [dshift; dscale] (x) a, dcontext (Cc) = SiLU'(context) . sum_l W_l^T [dshift; dscale].  The sum over
+ *   channels goes through `partial` (ptv3_pdnorm_partial_rows(total) x Cc floats, fully overwritten) and a final sum in
+ *   a fixed order: no atomics, two runs are bitwise equal.
+ * Capable: 1 <= C_l <= 4096, 1 <= Cc <= 1024, 1 <= L <= 4096.  16-byte loads along Cc when Cc % 4 == 0 and W is 16-byte
+ * aligned, 4-byte ones otherwise (decided per layer on the device; the results do not depend on it beyond rounding).
+ * Anything else, a NULL pointer included, is refused with PTV3_ERR_ARG before any launch. */
+#define PTV3_PDNORM_ROW 8 /* int64 entries per layer of `table`: &W, &b, &gamma, &beta, &mean, &var (0: NULL), off, C */
+int ptv3_pdnorm_capable(int C, int Cc);
+int ptv3_pdnorm_partial_rows(int64_t total);
+int ptv3_pdnorm_fwd(const int64_t* table, const int32_t* widths, int L, int Cc, const float* context, int fold,
+                    int has_stats, float eps, float* out0, float* out1, float* one_plus, void* stream);
+int ptv3_pdnorm_bwd(const int64_t* table, const int32_t* widths, int L, int Cc, const float* context,
+                    const float* d_out0, const float* d_out1, const float* one_plus, float* dW, float* db, float* dgamma,
+                    float* dbeta, float* partial, float* dcontext, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

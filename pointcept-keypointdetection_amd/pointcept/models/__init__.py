@@ -20,6 +20,7 @@ from .point_transformer_v2 import PointTransformerV2  # noqa: F401
 from .keypoint_ptv2 import KeypointPTv2  # noqa: F401
 from .keypoint_ptv3_plus import BlockPlus, PointTransformerV3Plus, KeypointPTv3Plus  # noqa: F401
 from .sparse_unet import SpUNetBase  # noqa: F401
+from .sparse_unet import PDBatchNorm, SpUNetBasePDNorm  # noqa: F401
 from .keypoint_sparse_unet import KeypointSparseUNet  # noqa: F401
 from .stratified_transformer import StratifiedTransformer  # noqa: F401
 from .keypoint_stratified_transformer import KeypointStratifiedTransformer  # noqa: F401

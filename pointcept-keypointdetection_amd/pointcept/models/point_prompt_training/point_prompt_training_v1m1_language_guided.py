@@ -103,6 +103,7 @@ class _PromptBase(nn.Module):
         if key not in self._index:
             self._index[key] = torch.tensor([index], device=device)
         data_dict["context"] = self.embedding_table(self._index[key])
+        data_dict["context_source"] = self.embedding_table.weight     # what SpUNet-v1m3 keys its cached folds on
         point = self.backbone(data_dict)
         return index, (point.feat if isinstance(point, Point) else point)
 

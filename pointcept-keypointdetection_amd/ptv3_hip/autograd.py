@@ -687,13 +687,16 @@ def layer_norm(x, weight, bias, eps):
     return LayerNormFn.apply(x, weight, bias, eps)
 
 
-def batch_norm_act(x, bn, act=ops.ACT_NONE):
+def batch_norm_act(x, bn, act=ops.ACT_NONE, weight=None, bias=None):
+    """`weight` / `bias`: an affine pair in place of bn's own (statistics, running buffers, momentum, eps, training flag
+    and sync_group stay bn's) - the BatchNorm of a PDBatchNorm, whose pair is the modulated one."""
     sync = getattr(bn, "sync_group", None)
     if sync is not None:
         import torch.distributed as dist
         if not (dist.is_available() and dist.is_initialized() and dist.get_world_size(None if sync is True else sync) > 1):
             sync = None
-    return BatchNormActFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training,
+    return BatchNormActFn.apply(x, bn.weight if weight is None else weight, bn.bias if bias is None else bias,
+                                bn.running_mean, bn.running_var, bn.training,
                                 bn.momentum if bn.momentum is not None else 0.1, bn.eps, act, sync)
 
 
@@ -989,3 +992,42 @@ class PGBiasLossFn(Function):
 def pg_bias_loss(bias_pred, coord, centroid, instance, ignore_index=-1):
     """-> (bias_l1_loss, bias_cosine_loss), 0-d with grad."""
     return PGBiasLossFn.apply(bias_pred, coord, centroid, instance, ignore_index)
+
+
+class PDNormModulationFn(Function):
+    """(gamma_eff_l, beta_eff_l) of every PDBatchNorm of a model from one context row: one launch forward
+    (ops.pdnorm_fwd), one launch plus the slab sum backward (ops.pdnorm_bwd); spconv_unet_v1m3_pdnorm.py:63-74,
+    DESIGN.md section 28.  `params` are the tensors the table points at - the L weights, the L biases and, with affine
+    BatchNorms, the L gammas and the L betas - so that the tape reaches them; their gradients are views of packed
+    buffers.  Returns 2 L tensors, views of two packed buffers: the L gamma_eff, then the L beta_eff."""
+
+    @staticmethod
+    def forward(ctx, tab, context, *params):
+        ctx_row = context.detach().float().contiguous().view(-1)
+        out0, out1, one_plus = ops.pdnorm_fwd(tab, ctx_row)
+        ctx.tab, ctx.shape, ctx.cdtype = tab, context.shape, context.dtype
+        # the backward reads the parameters through the table: saving them (no copy) makes an in-place change between
+        # forward and backward an error, as it is for torch's own Linear
+        ctx.save_for_backward(ctx_row, one_plus, *params)
+        return tuple(out0.split(tab.width_list)) + tuple(out1.split(tab.width_list))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        tab = ctx.tab
+        ctx_row, one_plus = ctx.saved_tensors[:2]
+        L, widths = tab.L, tab.width_list
+        parts = [g.float() if g is not None else one_plus.new_zeros(widths[i % L]) for i, g in enumerate(grads)]
+        d = torch.cat(parts)
+        dW, db, dgamma, dbeta, dctx = ops.pdnorm_bwd(tab, ctx_row, d[:tab.total], d[tab.total:], one_plus)
+        rows = [2 * c for c in widths]
+        out = list(dW.split(rows)) + list(db.split(rows))
+        if tab.affine:
+            out += list(dgamma.split(widths)) + list(dbeta.split(widths))
+        return (None, dctx.view(ctx.shape).to(ctx.cdtype), *out)
+
+
+def pdnorm_modulation(tab, context, params):
+    """-> (list of L gamma_eff, list of L beta_eff); `params` as PDNormModulationFn takes them."""
+    out = PDNormModulationFn.apply(tab, context, *params)
+    return out[:tab.L], out[tab.L:]
+

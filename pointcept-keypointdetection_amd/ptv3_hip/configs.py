@@ -254,6 +254,25 @@ PPT_V1M2_TINY_CFG = dict(
     context_channels=256, conditions=("A", "B", "C"), num_classes=(5, 7, 3), backbone_mode=False,
 )
 
+# Point Prompt Training over the sparse U-Net: the `model` dict of configs/scannet/semseg-ppt-v1m1-0-sc-st-spunet.py:17-55
+# (class_name and valid_index are the class defaults there and here), and the tiny SpUNet-v1m3 of the fixture
+# tests/golden/make_golden_spunet_pdnorm.py
+PPT_SPUNET_SCANNET_CFG = dict(
+    type="PPT-v1m1",
+    backbone=dict(type="SpUNet-v1m3", in_channels=6, num_classes=0, base_channels=32, context_channels=256,
+                  channels=(32, 64, 128, 256, 256, 128, 96, 96), layers=(2, 3, 4, 6, 2, 2, 2, 2), enc_mode=False,
+                  conditions=("ScanNet", "S3DIS", "Structured3D"), zero_init=False, norm_decouple=True,
+                  norm_adaptive=True, norm_affine=True),
+    criteria=[dict(type="CrossEntropyLoss", loss_weight=1.0, ignore_index=-1)], backbone_out_channels=96,
+    context_channels=256, conditions=("Structured3D", "ScanNet", "S3DIS"), template="[x]", clip_model="ViT-B/16",
+    backbone_mode=False,
+)
+SPUNET_PDNORM_TINY_CFG = dict(
+    type="SpUNet-v1m3", in_channels=4, num_classes=0, base_channels=16, context_channels=24,
+    channels=(16, 32, 32, 64, 64, 32, 16, 16), layers=(1, 2, 1, 1, 1, 1, 2, 1), enc_mode=False,
+    conditions=("A", "B", "C"), zero_init=False, norm_decouple=True, norm_adaptive=True, norm_affine=True,
+)
+
 # Sonata pretraining: the `model` dict of configs/sonata/pretrain-sonata-v1m1-0-base.py:21-79, and a tiny one (three
 # stages, up-cast back to the input level, 100 prototypes; no order shuffle, drop path or jitter, so that the patch
 # permutation is the only random draw of a step)

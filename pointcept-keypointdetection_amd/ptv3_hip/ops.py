@@ -3239,3 +3239,85 @@ def insseg_associate(masks, code, g, idx=None):
     lib.check(lib.ptv3_insseg_associate(_p(masks), _EV_MASK[masks.dtype], p, nm, _p(col_start), _p(code), n, g, _p(inter),
                                         _p(vert), _p(void), _stream()), "ptv3_insseg_associate")
     return inter, vert, void
+
+
+# ---------------------------------------------------------------------------------------------
+# modulation of every PDBatchNorm of SpUNet-v1m3 in one launch (csrc/pdnorm.hip)
+# ---------------------------------------------------------------------------------------------
+def pdnorm_capable(c, cc):
+    """(layer width C, context width Cc) ptv3_pdnorm_fwd / _bwd cover: 1 <= C <= 4096, 1 <= Cc <= 1024."""
+    return bool(lib.ptv3_pdnorm_capable(int(c), int(cc)))
+
+
+def pdnorm_table(layers):
+    """layers: one (W (2C, Cc), b (2C), gamma (C) | None, beta (C) | None, mean (C) | None, var (C) | None) per
+    PDBatchNorm, fp32 on one device -> the device table of pointers and channel offsets the kernels walk
+    (rows of PTV3_PDNORM_ROW int64), with the host copy of the widths.  The table holds addresses, not values: an in-place update of
+    a parameter needs no new table, a parameter replaced by another tensor does (`key` is what to compare)."""
+    from .lib import PTV3_PDNORM_ROW
+    if len(layers) == 0:
+        raise RuntimeError("pdnorm_table: no layers")
+    cc = layers[0][0].shape[1]
+    rows, widths, offs, off = [], [], [], 0
+    for i, (w, b, gamma, beta, mean, var) in enumerate(layers):
+        _chk(w, f"pdnorm_table: W[{i}]", torch.float32, 2)
+        _chk(b, f"pdnorm_table: b[{i}]", torch.float32, 1)
+        c = b.shape[0] // 2
+        if w.shape != (2 * c, cc) or b.shape[0] != 2 * c:
+            raise RuntimeError(f"pdnorm_table: layer {i}: W {tuple(w.shape)} / b {tuple(b.shape)}, expected (2C, {cc}) / (2C)")
+        for t, nm in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (var, "var")):
+            _chk(t, f"pdnorm_table: {nm}[{i}]", torch.float32, 1)
+            if t is not None and t.shape[0] != c:
+                raise RuntimeError(f"pdnorm_table: layer {i}: {nm} has {t.shape[0]} entries, expected {c}")
+        rows.append([w.data_ptr(), b.data_ptr(), _p(gamma) or 0, _p(beta) or 0, _p(mean) or 0, _p(var) or 0, off, c])
+        widths.append(c)
+        offs.append(off)
+        off += c
+    assert len(rows[0]) == PTV3_PDNORM_ROW
+    table = torch.tensor(rows, dtype=torch.int64).to(layers[0][0].device)
+    return SimpleNamespace(table=table, widths=(ctypes.c_int32 * len(widths))(*widths), width_list=widths, offs=offs,
+                           L=len(layers), cc=cc, total=off, key=pdnorm_table_key(layers),
+                           has_stats=all(ly[4] is not None and ly[5] is not None for ly in layers),
+                           affine=all(ly[2] is not None and ly[3] is not None for ly in layers))
+
+
+def pdnorm_table_key(layers):
+    """the addresses a table of these layers would hold"""
+    return tuple(0 if t is None else t.data_ptr() for ly in layers for t in ly)
+
+
+def pdnorm_fwd(tab, context, fold=False, eps=0.0, save=True):
+    """One launch for all layers of `tab`: -> (out0, out1, 1 + scale | None), packed over sum(C) in layer order.
+    fold = False: out0 = gamma (1 + scale), out1 = beta (1 + scale) + shift.  fold = True: the same folded with the
+    table's running statistics into the (bn_scale, bn_shift) of the conv epilogues."""
+    _chk(context, "pdnorm_fwd: context", torch.float32)
+    if context.numel() != tab.cc:
+        raise RuntimeError(f"pdnorm_fwd: context has {context.numel()} entries, the layers take {tab.cc}")
+    dev = context.device
+    out0 = torch.empty(tab.total, dtype=torch.float32, device=dev)
+    out1 = torch.empty(tab.total, dtype=torch.float32, device=dev)
+    one_plus = torch.empty(tab.total, dtype=torch.float32, device=dev) if save else None
+    lib.check(lib.ptv3_pdnorm_fwd(_p(tab.table), tab.widths, tab.L, tab.cc, _p(context), int(bool(fold)),
+                                  int(tab.has_stats), float(eps), _p(out0), _p(out1), _p(one_plus), _stream()),
+              "ptv3_pdnorm_fwd")
+    return out0, out1, one_plus
+
+
+def pdnorm_bwd(tab, context, d_out0, d_out1, one_plus):
+    """-> (dW (2 sum C, Cc), db (2 sum C), dgamma (sum C) | None, dbeta (sum C) | None, dcontext (Cc)): layer l's dW / db
+    start at row 2 off_l.  Two launches, no atomics."""
+    for t, nm in ((context, "context"), (d_out0, "d_out0"), (d_out1, "d_out1"), (one_plus, "one_plus")):
+        _chk(t, f"pdnorm_bwd: {nm}", torch.float32)
+    if d_out0.numel() != tab.total or d_out1.numel() != tab.total or one_plus.numel() != tab.total:
+        raise RuntimeError(f"pdnorm_bwd: the packed gradients must have {tab.total} entries")
+    dev = context.device
+    dW = torch.empty((2 * tab.total, tab.cc), dtype=torch.float32, device=dev)
+    db = torch.empty(2 * tab.total, dtype=torch.float32, device=dev)
+    dgamma = torch.empty(tab.total, dtype=torch.float32, device=dev) if tab.affine else None
+    dbeta = torch.empty(tab.total, dtype=torch.float32, device=dev) if tab.affine else None
+    partial = torch.empty((lib.ptv3_pdnorm_partial_rows(tab.total), tab.cc), dtype=torch.float32, device=dev)
+    dctx = torch.empty(tab.cc, dtype=torch.float32, device=dev)
+    lib.check(lib.ptv3_pdnorm_bwd(_p(tab.table), tab.widths, tab.L, tab.cc, _p(context), _p(d_out0), _p(d_out1),
+                                  _p(one_plus), _p(dW), _p(db), _p(dgamma), _p(dbeta), _p(partial), _p(dctx), _stream()),
+              "ptv3_pdnorm_bwd")
+    return dW, db, dgamma, dbeta, dctx
